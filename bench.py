@@ -21,6 +21,10 @@ Prints ONE JSON line (rank 0) with the driver contract fields plus
   "cpu_baseline": the CPU oracle (oracle/torch_ref.py = restatement of the reference's
                   math path + oracle C rANS) timed on this box's host cores on a bounded
                   sample (rank 0, N = 1 only).
+
+--dump-outputs DIR writes what the last timed step returned (rank 0) as float32 DIR/<name>.npy, at most 64 MB: the y / z
+streams and z_shape in full and a fixed seeded sample of x_hat.  The same arguments give the same inputs (seeded frames
+and weights), so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -242,6 +246,28 @@ def reference_pinned(seed, strings, suffix=""):
             "z_bytes_reference": int(g["z_string"].size)}
 
 
+DUMP_XHAT_SAMPLES = 1 << 22      # 16 MB of x_hat; the streams of one frame add ~20 MB as float32
+
+
+def dump_outputs(out_dir, out, x_hat, limit_bytes=64 << 20):
+    """--dump-outputs: what a caller of compress() -> decompress() received in the last timed step, as float32 .npy files
+    that two builds can compare array for array - y_stream / z_stream (the .bin strings, one byte per element), z_shape,
+    and x_hat_sample: x_hat at DUMP_XHAT_SAMPLES fixed positions (numpy PCG64 seed 0, sorted; x_hat itself is 1.11 GB)."""
+    import numpy as np
+    arrays = {"y_stream": np.frombuffer(out["strings"][0][0], np.uint8).astype(np.float32),
+              "z_stream": np.frombuffer(out["strings"][1][0], np.uint8).astype(np.float32),
+              "z_shape": np.asarray(out["z_shape"], np.float32)}
+    flat = x_hat.reshape(-1)
+    pos = np.sort(np.random.default_rng(0).integers(0, flat.numel(), DUMP_XHAT_SAMPLES))
+    arrays["x_hat_sample"] = flat[torch.from_numpy(pos).to(flat.device)].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit_bytes:
+        raise RuntimeError(f"--dump-outputs: {total} bytes > {limit_bytes}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def host_phase_summary(log):
     """mean ms per frame of the host (rANS) phases from VAEformer.host_log: encode y + z | decode z | decode y."""
     out = {}
@@ -420,6 +446,9 @@ def error_line(exc, stage):
 
 
 STAGE = ["startup"]     # where main() is (the error line names it)
+# the measured terms of single_frame_budget(); `encode_other` / `decode_other` are what they leave of the totals
+ENCODE_TERMS = ("h2d", "g1_g_a_and_latent_side", "g1b_other_gpu_phases", "h1_rans_encode", "bin_write")
+DECODE_TERMS = ("h2z_rans_decode_z", "g2_h_s_indexes", "h2y_rans_decode_y", "g3_g_s")
 
 
 def single_frame_budget(api, host_frame, reps=4):
@@ -468,14 +497,15 @@ def single_frame_budget(api, host_frame, reps=4):
                    "decode_total": t3 - t2, "h2z_rans_decode_z": h_dec.get("dec_z", 0.0),
                    "g2_h_s_indexes": g_dec[0] if g_dec else 0.0, "h2y_rans_decode_y": h_dec.get("dec_y", 0.0),
                    "g3_g_s": sum(g_dec[1:])}
-            row["encode_other"] = row["encode_total"] - sum(row[k] for k in ("h2d", "g1_g_a_and_latent_side", "g1b_other_gpu_phases", "h1_rans_encode", "bin_write"))
-            row["decode_other"] = row["decode_total"] - sum(row[k] for k in ("h2z_rans_decode_z", "g2_h_s_indexes", "h2y_rans_decode_y", "g3_g_s"))
             rows.append(row)
     finally:
         net.phase_log = net.host_log = None
         shutil.rmtree(tmp, ignore_errors=True)
     use = rows[1:] or rows
     med = {k: 1e3 * sorted(r[k] for r in use)[len(use) // 2] for k in rows[0]}
+    # `other` from the medians (each key's median may come from a different rep): the budget adds up to its totals
+    med["encode_other"] = med["encode_total"] - sum(med[k] for k in ENCODE_TERMS)
+    med["decode_other"] = med["decode_total"] - sum(med[k] for k in DECODE_TERMS)
     med["frames_per_s"] = 1e3 / (med["encode_total"] + med["decode_total"])
     return med
 
@@ -666,7 +696,12 @@ def main():
                          "baseline leg lifts the bind again")
     ap.add_argument("--inflight", type=int, default=rc0.inflight,
                     help="frames in flight per GPU (host rANS of one frame overlaps GPU work of the others)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step returned (rank 0) as DIR/<name>.npy: "
+                         "the y / z streams and z_shape in full, a fixed seeded sample of x_hat (dump_outputs())")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     force_launch = os.environ.get("CRA5_FORCE_SELF_LAUNCH") == "1"    # tests: the launcher path on a 1-GPU box
     if (args.gpus > 1 or force_launch) and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -760,10 +795,13 @@ def main():
     # box the first use of a torch kernel pages its code object in from a cold disk cache (measured: 23.0-24.3
     # frames/s in the first process on a box vs 26.3-27.0 in the following ones when the probe first ran inside
     # the timed region).
-    def round_trip(x):
+    def decoded(x):
         out = net.compress(x)
         out = dict(out, n_escape=net.last_n_escape())      # (bench-side copy: compress() returns the reference's two keys)
-        x_hat = net.decompress(out["strings"], out["z_shape"])["x_hat"]
+        return out, net.decompress(out["strings"], out["z_shape"])["x_hat"]
+
+    def round_trip(x):
+        out, x_hat = decoded(x)
         return out, finite_probe(x_hat)
 
     # the timed region's scheduling mode applies to the warm-up too (it used to run in the default exclusive mode:
@@ -837,7 +875,19 @@ def main():
     t0 = time.perf_counter()
     # EXACTLY K steps = K full round trips; up to `inflight` frames overlap, all K complete
     # (streams synchronised, x_hat materialised) before the clock stops.
-    results = pipe.map(round_trip, [frames[i % pool] for i in range(args.steps)])
+    if args.dump_outputs is None:
+        results = pipe.map(round_trip, [frames[i % pool] for i in range(args.steps)])
+    else:
+        # the same steps; the last one also keeps a reference to its x_hat (no extra work inside the region)
+        last = {}
+
+        def timed_step(item):
+            i, x = item
+            out, x_hat = decoded(x)
+            if i == args.steps - 1:
+                last["out"], last["x_hat"] = out, x_hat
+            return out, finite_probe(x_hat)
+        results = pipe.map(timed_step, [(i, frames[i % pool]) for i in range(args.steps)])
     if clk is not None:
         clk.stop()               # joins the probe thread; its last 50 us probe is covered by the sync below
     torch.cuda.synchronize()
@@ -853,6 +903,10 @@ def main():
               "how": "timed_region: a one-wave probe every 5 ms beside the workload (cra5_clock_probe: shader cycles over a "
                      "50 us window of the 100 MHz wall clock, on whichever CU the wave lands).  hwmon: amdgpu sysfs files read "
                      "every 20 ms by a host thread (`static` = they did not move)"}
+    if args.dump_outputs is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last["out"], last["x_hat"])
+        last.clear()
     rows = [D.frame_stats(my_frames[i], out["strings"], out.get("n_escape", [-1])[0]) for i, (out, _) in enumerate(results)]
     assert all(probe_ok(ok) for _, ok in results)
     # frames that re-use a pool tensor must reproduce its streams byte for byte (sizes + CRC): a race or a

@@ -5,6 +5,8 @@ deterministic synthetic weights of cra5_amd/synth.py into the reference model an
 dumps small input/output fixtures (data only) next to this script:
 
   pmf_cdf.json          outputs of the reference's ops.cpp (compiled as oracle/_ref/_CXX)
+  pmf_cdf_random.npz    (--stage pmf_random) the same ops.cpp on 200 seeded random pmfs of up to
+                        300 entries (the draw of tests/test_oracle_vs_golden.py::test_live_reference_cxx_if_built)
   state_keys.json       state-dict key -> shape of the 268 model and the thin model
   tables_default.npz    GaussianConditional.update() tables for get_scale_table() and
                         EntropyBottleneck.update() tables at the synthetic EB params
@@ -65,6 +67,28 @@ THIN_PRIOR_KW = dict(z_dim=16, embed_dim=144, depth=4, num_heads=2, interval=1, 
                      window=False, drop_path_rate=0., round_padding=True, pad_attn_mask=True,
                      test_pos_mode='learnable_simple_interpolate', lms_checkpoint_train=False,
                      img_size=(72, 144))
+
+
+def random_pmfs(seed=7, count=200):
+    """The pmfs of tests/test_oracle_vs_golden.py::test_live_reference_cxx_if_built (same draw, same order)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(count):
+        n = int(rng.integers(1, 300))
+        p = rng.random(n).astype(np.float32) ** int(rng.integers(1, 10))
+        p /= max(p.sum(), 1e-30)
+        if p.sum() == 0:
+            continue
+        out.append(p)
+    return out
+
+
+def stage_pmf_random():
+    pmfs = random_pmfs()
+    cdfs = [np.asarray(REF_CXX.pmf_to_quantized_cdf(p.tolist(), 16), dtype=np.int32) for p in pmfs]
+    np.savez_compressed(os.path.join(HERE, "pmf_cdf_random.npz"),
+                        pmf=np.concatenate(pmfs), pmf_len=np.array([p.size for p in pmfs], np.int32),
+                        cdf=np.concatenate(cdfs), cdf_len=np.array([c.size for c in cdfs], np.int32))
 
 
 def build_thin():
@@ -718,4 +742,5 @@ if __name__ == "__main__":
     for s in a.stage:
         dict(small=stage_small, thin=stage_thin, thin_flip=stage_thin_flip, thin_cands_pack=stage_thin_cands_pack, thin_search=stage_thin_search, thin_cands=stage_thin_cands, thin2=stage_thin2, full=stage_full, full159=stage_full159, stats=stage_stats,
              cnn=stage_cnn, cnn_relu=stage_cnn_relu, ints=stage_ints, thin_matched=stage_thin_matched,
+             pmf_random=stage_pmf_random,
              thin64=lambda: stage_fp64("thin"), full64=lambda: stage_fp64("full"))[s]()

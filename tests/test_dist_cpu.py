@@ -211,6 +211,31 @@ def test_bench_committed_reference_reads_the_profile_of_its_own_precision():
         assert b["avg_launch_ms"] < a["avg_launch_ms"]
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_cap(tmp_path):
+    """`bench.py --dump-outputs DIR` (dump_outputs): the streams in full, z_shape and a fixed x_hat sample, float32 .npy
+    only, at most 64 MB, and the same files for the same outputs; over the cap it refuses instead of writing."""
+    import numpy as np
+    import pytest
+    import bench
+    x_hat = torch.randn((1, 268, 721, 1440), generator=torch.Generator().manual_seed(3))
+    y, z = bytes(range(256)) * 17000, b"\x05\xfa" * 80000
+    out = {"strings": [[y], [z]], "z_shape": (18, 36)}
+    bench.dump_outputs(str(tmp_path / "a"), out, x_hat)
+    bench.dump_outputs(str(tmp_path / "b"), out, x_hat)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["x_hat_sample.npy", "y_stream.npy", "z_shape.npy", "z_stream.npy"]
+    arrays = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype == np.float32 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert bytes(arrays["y_stream.npy"].astype(np.uint8)) == y and bytes(arrays["z_stream.npy"].astype(np.uint8)) == z
+    assert arrays["z_shape.npy"].tolist() == [18, 36] and arrays["x_hat_sample.npy"].size == bench.DUMP_XHAT_SAMPLES
+    pos = np.sort(np.random.default_rng(0).integers(0, x_hat.numel(), bench.DUMP_XHAT_SAMPLES))
+    assert np.array_equal(arrays["x_hat_sample.npy"], x_hat.reshape(-1).numpy()[pos])
+    assert all(np.array_equal(arrays[n], np.load(tmp_path / "b" / n)) for n in names)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "c"), out, x_hat, limit_bytes=1 << 20)
+    assert not (tmp_path / "c").exists()
+
+
 # ---- round 6: first-contact hardening of the N-rank job (VERDICT r5 item 5) -------------------------------------------------
 
 

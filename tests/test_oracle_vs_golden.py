@@ -35,20 +35,27 @@ def test_pmf_to_cdf_matches_reference_cxx(golden_dir):
                 cbind.pmf_to_cdf(np.array(vals, dtype=np.float32))
 
 
-def test_live_reference_cxx_if_built():
-    """When oracle/_ref/_CXX (the reference's ops.cpp compiled where it lies) is present,
-    cross-check on fresh random pmfs as well."""
-    cxx = cbind.ref_cxx()
-    if cxx is None:
-        pytest.skip("oracle/_ref not built")
+def test_live_reference_cxx_if_built(golden_dir):
+    """200 seeded random pmfs: the oracle == the reference's ops.cpp outputs stored in pmf_cdf_random.npz
+    (tests/golden/make_golden.py --stage pmf_random), and == oracle/_ref/_CXX live when it has been built."""
+    g = np.load(f"{golden_dir}/pmf_cdf_random.npz")
+    pmfs = np.split(g["pmf"], np.cumsum(g["pmf_len"])[:-1])
+    cdfs = np.split(g["cdf"], np.cumsum(g["cdf_len"])[:-1])
     rng = np.random.default_rng(7)
+    drawn = []
     for _ in range(200):
         n = int(rng.integers(1, 300))
         p = rng.random(n).astype(np.float32) ** int(rng.integers(1, 10))
         p /= max(p.sum(), 1e-30)
         if p.sum() == 0:
             continue
-        assert cbind.pmf_to_cdf(p).tolist() == list(cxx.pmf_to_quantized_cdf(p.tolist(), 16))
+        drawn.append(p)
+    assert len(drawn) == len(pmfs) == len(cdfs) and all(np.array_equal(a, b) for a, b in zip(drawn, pmfs))
+    cxx = cbind.ref_cxx()
+    for p, c in zip(pmfs, cdfs):
+        assert cbind.pmf_to_cdf(p).tolist() == c.tolist()
+        if cxx is not None:
+            assert c.tolist() == list(cxx.pmf_to_quantized_cdf(p.tolist(), 16))
 
 
 def test_tables_match_reference(golden_dir):

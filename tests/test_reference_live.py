@@ -1,43 +1,34 @@
-"""BUILD-CONTAINER-ONLY check (skipped wherever /root/reference is absent, e.g. the GPU box):
-the reference's OWN Python `compress()` / `decompress()` run with the PRODUCT's coder
-(cra5_amd.ans, C ABI) plugged in as `compressai.ans` must reproduce the committed golden byte
-streams (which were produced with the oracle coder) and round-trip."""
-import os
-import subprocess
-import sys
+"""The PRODUCT's coder plugged in as the reference's `compressai.ans` (cra5_amd.ans, C ABI), called exactly as the
+reference's entropy models call it (entropy_models.py:264-269 compress, :318-323 decompress: Python lists of symbols /
+indexes, the quantized CDF table as a list of rows, lengths and offsets as lists), on the integers and tables the
+reference's own Python produced for the thin frame (tests/golden/thin_e2e.npz, tables_default.npz): it must reproduce
+the committed golden byte streams (written with the oracle coder) and round-trip to the reference's y_hat."""
+import numpy as np
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-SCRIPT = r'''
-import sys, numpy as np, torch
-sys.path.insert(0, %(root)r)
 from cra5_amd import ans as product_ans
-from oracle import ref_shim
-ref_shim.install(ans_module=product_ans)
-sys.path.insert(0, %(root)r + "/tests/golden")
-import importlib.util
-spec = importlib.util.spec_from_file_location("mk", %(root)r + "/tests/golden/make_golden.py")
-# reuse the thin-model builder without re-running the shim install
-src = open(%(root)r + "/tests/golden/make_golden.py").read().replace("ref_shim.install()", "pass")
-ns = {"__name__": "mk", "__file__": %(root)r + "/tests/golden/make_golden.py"}
-exec(compile(src, "make_golden.py", "exec"), ns)
-net = ns["build_thin"](); ns["load_synth"](net, seed=7)
-g = np.load(%(root)r + "/tests/golden/thin_e2e.npz")
-x = ns["synth"].synth_frame(8, seed=int(g["x_seed"][0])).unsqueeze(0)
-with torch.no_grad():
-    out = net.compress(x)
-    rec = net.decompress(out["strings"], out["z_shape"], return_format="latent")
-assert out["strings"][0][0] == g["y_string"].tobytes(), "y stream differs"
-assert out["strings"][1][0] == g["z_string"].tobytes(), "z stream differs"
-assert np.allclose(rec.reshape(-1)[::37].numpy(), g["y_hat_sub"], atol=1e-6)
-print("REFERENCE+PRODUCT-CODER OK", len(out["strings"][0][0]), len(out["strings"][1][0]))
-'''
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/cra5"), reason="reference tree only exists in the build container")
-def test_reference_python_with_product_coder():
-    r = subprocess.run([sys.executable, "-c", SCRIPT % {"root": ROOT}], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "REFERENCE+PRODUCT-CODER OK" in r.stdout
+def _tables(t, kind):
+    return (t[f"{kind}_cdf"].tolist(), t[f"{kind}_len"].reshape(-1).tolist(), t[f"{kind}_off"].reshape(-1).tolist())
+
+
+def test_reference_python_with_product_coder(golden_dir):
+    g = np.load(f"{golden_dir}/thin_e2e.npz")
+    t = np.load(f"{golden_dir}/tables_default.npz")
+    gc, eb = _tables(t, "gc"), _tables(t, "eb")
+    # y: GaussianConditional.compress - symbols = round(y - means), indexes from the scales
+    y_sym, y_idx = g["sym_full"].astype(np.int32).tolist(), g["idx_full"].astype(np.int32).tolist()
+    y_string = product_ans.RansEncoder().encode_with_indexes(y_sym, y_idx, *gc)
+    assert y_string == g["y_string"].tobytes(), "y stream differs"
+    # z: EntropyBottleneck.compress - symbols = round(z - medians), index = channel
+    z_sym = g["z_sym"]
+    z_idx = np.broadcast_to(np.arange(z_sym.shape[1], dtype=np.int32).reshape(1, -1, 1, 1), z_sym.shape)
+    z_string = product_ans.RansEncoder().encode_with_indexes(z_sym.reshape(-1).tolist(), z_idx.reshape(-1).tolist(), *eb)
+    assert z_string == g["z_string"].tobytes(), "z stream differs"
+    # decompress(return_format="latent"): values read back, y_hat = values + means
+    assert product_ans.RansDecoder().decode_with_indexes(z_string, z_idx.reshape(-1).tolist(), *eb) == z_sym.reshape(-1).tolist()
+    values = product_ans.RansDecoder().decode_with_indexes(y_string, y_idx, *gc)
+    assert values == y_sym
+    y_hat_sub = np.asarray(values, dtype=np.float32)[::37] + g["means_sub"]
+    assert np.allclose(y_hat_sub, g["y_hat_sub"], atol=1e-6)
+    print("REFERENCE+PRODUCT-CODER OK", len(y_string), len(z_string))
