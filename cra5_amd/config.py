@@ -12,8 +12,8 @@ Not settings, and therefore not here:
     `.resolve_on_gpu`, `.attn_balanced`, `.f16_layout`): plain attributes a test flips, no environment variable;
   * test hooks (CRA5_TEST_*, CRA5_SHARE_GPU, CRA5_FORCE_DIST, CRA5_DIST_BACKEND) and CRA5_LIB (which library file to
     load: a build matter, cra5_amd/_lib.py).
-The native library reads NO environment variable (experiment overrides exist only in variant builds:
-tools/build_variant.sh -DCRA5_TUNING_ENV).
+The native library reads NO environment variable (only the -DCRA5_GEMM_TRACE variant build that tools/gemm_trace.py
+uses reads a forced GEMM tile).
 """
 import dataclasses
 import os

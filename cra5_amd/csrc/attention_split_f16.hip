@@ -64,8 +64,8 @@ __device__ __forceinline__ int token_of(const WinGeom &g, int wr, int wc, int t)
 }
 
 #ifdef CRA5_ATTN_TRACE
-// debug build only (tools/attn_trace.py): per work-group (classic) / per unit (PERSIST) wall-clock stamps {start, key loop
-// start, key loop end, end}, the key tiles of the unit and the shader cycles between start and end
+// debug build only (tools/attn_trace.py): per work-group wall-clock stamps {start, key loop start, key loop end, end}, the
+// key tiles of the work-group and the shader cycles between start and end
 __device__ unsigned long long g_attn_trace[6 * 8192];
 #define CRA5_ATRACE(SLOT, VAL)                                                                          \
   if (threadIdx.x == 0 && atrace_idx < 8192) g_attn_trace[atrace_idx * 6 + (SLOT)] = (VAL);
@@ -120,42 +120,18 @@ constexpr int WS_ROW = 68;   // floats per query of a partial: O[64], m, l, 2 pa
 // PLAIN (reduced-precision mode only, round 5): qkv rows, the pad row and the out_s rows are PLAIN f16 - element n at
 // half n of the row (row pitch unchanged: a plain row is the first half of a split row) - as the plain-output qkv GEMM
 // writes them and the plain-operand proj GEMM reads them: K / V tiles are staged as 128-byte instead of 256-byte rows.
-// PERSIST (round 6): windowed launches as ONE persistent 12-wave work-group per CU that walks a list of UNITS.  A
-// (window, head) pair has T = L / 32 wave-tiles of queries (18 for the model's 576-token windows): T / 12 FULL units
-// (12 wave-tiles x the whole key loop) and, for the T % 12 = 6 tiles that are left, one SPLIT unit - waves 0..5 run the
-// six tiles over the first half of the keys, waves 6..11 the SAME six tiles over the second half (two K / V tiles staged
-// per step, one per wave group), and the two un-normalised partials (m, l, O) are merged through LDS in fixed order
-// before the store.  Every wave of every unit is busy (the 4-wave form's fifth work-group of a pair was half empty), K / V
-// of a pair are staged 1.5 x instead of 5 x, a step runs 3 waves per SIMD behind ONE barrier domain like the whole-grid
-// launch, and the per-launch fixed cost (two rounds of prologue + epilogue under contention: 20 of 105 us) is paid once
-// per unit on a CU that has nothing else to wait for.  Units are dealt so that the work-groups that got one FULL unit
-// more take no SPLIT unit first (576 units on 256 CUs: 36 key steps at most, 30.4 on average).
-template <int NW, bool HI, bool GLOBAL, bool BAL = false, bool PLAIN = false, bool PERSIST = false>
+// Windowed launches are 4-wave work-groups, three per CU: attention_dispatch says why.
+template <int NW, bool HI, bool GLOBAL, bool BAL = false, bool PLAIN = false>
 __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void window_attention_split_kernel(
     const unsigned short *__restrict__ qkv, long ldq /* halves per row = 2*Kp */,
     const unsigned short *__restrict__ pad_row, float *__restrict__ out, unsigned short *__restrict__ out_s,
-    int Kp_out, int C, int heads, WinGeom g, int q_tiles /* PERSIST: number of windows */, float scale, BalArgs bal) {
+    int Kp_out, int C, int heads, WinGeom g, int q_tiles /* work-groups per (window, head) */, float scale, BalArgs bal) {
   static_assert(!BAL || GLOBAL, "the balanced schedule is for whole-grid launches");
   static_assert(!PLAIN || HI, "plain rows carry no lo plane");
-  static_assert(!PERSIST || (!GLOBAL && !BAL && NW % 2 == 0), "the persistent unit walk is for windowed launches");
   constexpr int NT = NW * 64;
   constexpr int PPR = PLAIN ? 8 : 16;             // 16-byte pieces per K (or V) row of one head: 64 d x (hi | hi + lo)
   constexpr int PIECES = 32 * PPR;                // 16-byte pieces per K (or V) tile
   constexpr int STG = (PIECES + NT - 1) / NT;
-  // PERSIST stages K / V by LDS-DMA (global_load_lds_dwordx4: no staging VGPRs, no ds_write pass) into a ring of NSTG
-  // stages per wave group, so that a tile is requested THREE key steps before its scores are due - one step of prefetch
-  // (registers) left all 12 waves of the CU waiting for the slowest L2-missing load at every barrier.  A stage is the K
-  // image followed by the V image, rows UN-padded (a DMA instruction writes 1 KB linearly: 4 split rows / 8 plain rows),
-  // 16-byte pieces XOR-swizzled through the per-lane SOURCE address so that the fragment reads stay conflict-free:
-  //   K (ds_read_b128, 16 consecutive rows per cycle):   piece ^ (row & 15)            [plain: piece ^ ((row >> 1) & 7)]
-  //   V (ds_read_b64_tr_b16, 4 consecutive rows x 64 B): piece ^ 4 (row & 3)           [plain: piece ^ 4 ((row >> 1) & 1)]
-  constexpr int ROWH = PLAIN ? 64 : 128;          // halves per K / V row image
-  constexpr int KIMG = 32 * ROWH;                 // halves per K (or V) tile image
-  constexpr int STAGE_H = 2 * KIMG;               // K image | V image
-  constexpr int NSTG = 4;
-  constexpr int NIG = PLAIN ? 8 : 16;             // DMA instructions per stage and wave group (K: first half, V: second)
-  constexpr int RPI = PLAIN ? 8 : 4;              // rows per DMA instruction
-  constexpr int NPW = (2 * NIG + NW - 1) / NW;    // most DMA instructions a wave issues per stage (SPLIT units: two groups)
 
   // [K hi][K lo] : 32 x KS ;  [V hi][V lo] : 32 x VS (row-major like K, transposed by the READ)
   constexpr int KPL = 32 * KS + 32;   // K plane stride (halves): +64 B so hi/lo planes hit different bank halves
@@ -163,8 +139,8 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
   // two K buffers and two V^T buffers: tile j+1's scores are issued to the matrix pipe BEFORE
   // the softmax of tile j, so K runs one tile ahead of V; one barrier per key tile.
   constexpr int KBUF = 2 * KPL, VBUF = 2 * VPL;
-  __shared__ __attribute__((aligned(16))) unsigned short lds[PERSIST ? 2 * NSTG * STAGE_H : 2 * KBUF + 2 * VBUF];
-  unsigned short *Ks = lds;                       // (PERSIST: wave group g's ring at lds + g * NSTG * STAGE_H)
+  __shared__ __attribute__((aligned(16))) unsigned short lds[2 * KBUF + 2 * VBUF];
+  unsigned short *Ks = lds;
   unsigned short *Vt = lds + 2 * KBUF;
   // windowed launches: byte offset (from qkv) of every window token's row, pad tokens -> the pad
   // row; built once per block so that the per-tile staging needs no division / multiply.
@@ -212,26 +188,23 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
         s = e;
       }
     }
-  } else if (!PERSIST) {
+  } else {
     const int pid = xcd_remap(blockIdx.x, gridDim.x);
     const int qt = pid % q_tiles;
     const int wh_id = pid / q_tiles;
     head = wh_id % heads;
     win = wh_id / heads;
     seg_tile0[0] = qt * NW;
-  } else {
-    head = 0;
-    win = 0;
   }
-  int wr = win / g.nwc, wc = win - wr * g.nwc;
+  const int wr = win / g.nwc, wc = win - wr * g.nwc;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
-  int hoff = head * HD;
+  const int hoff = head * HD;
   // halves offset of this head's q / k / v slice inside a split row (64 d = 2 chunks = 128 halves)
-  long qoff = (PLAIN ? 1L : 2L) * hoff, koff = (PLAIN ? 1L : 2L) * (C + hoff), voff = (PLAIN ? 1L : 2L) * (2 * C + hoff);
+  const long qoff = (PLAIN ? 1L : 2L) * hoff, koff = (PLAIN ? 1L : 2L) * (C + hoff), voff = (PLAIN ? 1L : 2L) * (2 * C + hoff);
 
-  if (!GLOBAL && !PERSIST) {
+  if (!GLOBAL) {
     const long long pad_delta = reinterpret_cast<const char *>(pad_row) - reinterpret_cast<const char *>(qkv);
     for (int t = tid; t < L; t += NT) {
       const int tok = token_of(g, wr, wc, t);
@@ -240,64 +213,16 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
   }
   constexpr bool IDLE_SKIP = !GLOBAL || BAL;
   bool tab_ready = GLOBAL;
-  // PERSIST: the unit walk of this work-group.  T wave-tiles per (window, head) pair = fg FULL units + (rem ? 1 : 0) unit
-  // of the rem tiles left (SPLIT when rem = NW / 2).  FULL units are dealt round-robin; the r = nF % G work-groups that got
-  // one more of them take no remainder unit before the other G - r have one each.
-  const int pu_T = L / 32, pu_fg = pu_T / NW, pu_rem = pu_T - pu_fg * NW;
-  const int pu_pairs = PERSIST ? q_tiles * heads : 0;
-  const int pu_nF = pu_pairs * pu_fg, pu_nH = pu_rem ? pu_pairs : 0;
-  const int pu_G = (int)gridDim.x, pu_r = pu_nF % pu_G;
-  const int pu_light = (pu_r && pu_G - pu_r > 0) ? pu_G - pu_r : pu_G;      // work-groups the remainder units rotate over
-  int pu_f = (int)blockIdx.x;                                                // next FULL unit of this work-group
-  int pu_h = (pu_light == pu_G) ? (int)blockIdx.x : ((int)blockIdx.x >= pu_r ? (int)blockIdx.x - pu_r : pu_nH);
 #pragma unroll 1
-  for (int seg = 0; PERSIST || seg < n_seg; ++seg) {
-  int tile0 = seg_tile0[PERSIST ? 0 : seg], n_active = seg_nact[PERSIST ? 0 : seg], j0 = seg_j0[PERSIST ? 0 : seg], j1 = seg_j1[PERSIST ? 0 : seg];
-  bool split = false;         // PERSIST: this unit runs its tiles twice, each wave group over half of the keys
-  if (PERSIST) {
-    int pair;
-    if (pu_f < pu_nF) {
-      pair = pu_f / pu_fg;
-      tile0 = (pu_f - pair * pu_fg) * NW;
-      n_active = NW;
-      pu_f += pu_G;
-    } else if (pu_h < pu_nH) {
-      pair = pu_h;
-      tile0 = pu_fg * NW;
-      split = (2 * pu_rem == NW) && (pu_T % 2 == 0);
-      n_active = pu_rem;
-      pu_h += pu_light;
-    } else {
-      break;
-    }
-    head = pair % heads;
-    win = pair / heads;
-    wr = win / g.nwc;
-    wc = win - wr * g.nwc;
-    hoff = head * HD;
-    qoff = (PLAIN ? 1L : 2L) * hoff;
-    koff = (PLAIN ? 1L : 2L) * (C + hoff);
-    voff = (PLAIN ? 1L : 2L) * (2 * C + hoff);
-    j0 = 0;
-    j1 = split ? pu_T / 2 : pu_T;
-    // the row-offset table of this unit's window (every wave is past the last barrier of the previous unit's key loop,
-    // after which nobody reads the table; the barrier below publishes it)
-    const long long pad_delta = reinterpret_cast<const char *>(pad_row) - reinterpret_cast<const char *>(qkv);
-    for (int t = tid; t < L; t += NT) {
-      const int tok = token_of(g, wr, wc, t);
-      tab[t] = (tok >= 0) ? (long long)tok * ldq * 2 : pad_delta;
-    }
-  }
+  for (int seg = 0; seg < n_seg; ++seg) {
+  const int tile0 = seg_tile0[seg], n_active = seg_nact[seg], j0 = seg_j0[seg], j1 = seg_j1[seg];
 #ifdef CRA5_ATTN_TRACE
-  const int atrace_idx = PERSIST ? (int)blockIdx.x * 4 + seg : (GLOBAL ? 8192 : (int)blockIdx.x);
+  const int atrace_idx = GLOBAL ? 8192 : (int)blockIdx.x;
   const unsigned long long atrace_c0 = clock64();
 #endif
   CRA5_ATRACE(0, wall_clock64());
-  // SPLIT unit: wave group gw = wave / (NW / 2) runs tiles tile0 + wave % (NW / 2) over key tiles [gw * n_tiles, + n_tiles)
-  const int gw = (PERSIST && split) ? wave / (NW / 2) : 0;
-  const int wq = (PERSIST && split) ? wave - gw * (NW / 2) : wave;
-  const int tq = (tile0 + wq) * 32 + l31;
-  const int q_tok = (tq < L && wq < n_active) ? token_of(g, wr, wc, tq) : -1;
+  const int tq = (tile0 + wave) * 32 + l31;
+  const int q_tok = (tq < L && wave < n_active) ? token_of(g, wr, wc, tq) : -1;
   const bool wave_active = __any(q_tok >= 0);
   // (also publishes the row-offset table of a windowed launch; between two segments every wave is past the last
   // barrier of the previous key loop, after which nobody reads the K / V buffers any more)
@@ -366,8 +291,8 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
   reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(qkv) + tab[(JJ)*32 + (ROW)])
   // (waves whose pieces fall past the 512 of a tile - 4 of 12, or the second piece of 4 of 6 - skip the
   // loads and their address arithmetic altogether: the conditions are wave-uniform)
-  const bool stage0 = !PERSIST && ((NT <= PIECES) || (tid < PIECES));   // (PERSIST: no register staging at all)
-  const bool stage1 = !PERSIST && TWO && (tid + NT < PIECES);
+  const bool stage0 = (NT <= PIECES) || (tid < PIECES);
+  const bool stage1 = TWO && (tid + NT < PIECES);
 #define CRA5_K_LOAD(J)                                                                    \
   if (stage0) {                                                                           \
     if (GLOBAL) {                                                                         \
@@ -400,7 +325,7 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
 #define CRA5_K_STORE1(P, BUF)                                                             \
   {                                                                                       \
     const int idx = tid + (P)*NT;                                                         \
-    if (!PERSIST && idx < PIECES) {                                                       \
+    if (idx < PIECES) {                                                                   \
       const int row = idx / PPR, piece = idx % PPR;                                       \
       const int plane = PLAIN ? 0 : (piece >> 2) & 1, d0 = PLAIN ? 8 * piece : 32 * (piece >> 3) + 8 * (piece & 3); \
       *reinterpret_cast<uint4 *>(Ks + (BUF)*KBUF + plane * KPL + row * KS + d0) = sk##P;  \
@@ -410,7 +335,7 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
 #define CRA5_V_STORE1(P, BUF)                                                             \
   {                                                                                       \
     const int idx = tid + (P)*NT;                                                         \
-    if (!PERSIST && idx < PIECES) {                                                       \
+    if (idx < PIECES) {                                                                   \
       const int row = idx / PPR, piece = idx % PPR;                                       \
       const int plane = PLAIN ? 0 : (piece >> 2) & 1, d0 = PLAIN ? 8 * piece : 32 * (piece >> 3) + 8 * (piece & 3); \
       *reinterpret_cast<uint4 *>(Vt + (BUF)*VBUF + plane * VPL + row * VS + d0) = sv##P;  \
@@ -424,10 +349,8 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
     f32x16 acc_;                                                                          \
     _Pragma("unroll") for (int r = 0; r < 16; ++r) acc_[r] = 0.f;                         \
     _Pragma("unroll") for (int st = 0; st < 4; ++st) {                                    \
-      const half8 kh = PERSIST ? *reinterpret_cast<const half8 *>(ring + (KB)*STAGE_H + koffs[0][st])      \
-                               : *reinterpret_cast<const half8 *>(k_base + (KB)*KBUF + 16 * st);            \
-      const half8 kl = PERSIST ? *reinterpret_cast<const half8 *>(ring + (KB)*STAGE_H + koffs[PLAIN ? 0 : 1][st]) \
-                               : *reinterpret_cast<const half8 *>(k_base + (KB)*KBUF + KPL + 16 * st);      \
+      const half8 kh = *reinterpret_cast<const half8 *>(k_base + (KB)*KBUF + 16 * st);     \
+      const half8 kl = *reinterpret_cast<const half8 *>(k_base + (KB)*KBUF + KPL + 16 * st); \
       if (!HI) {                                                                          \
         acc_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[st], acc_, 0, 0, 0);         \
         acc_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[st], acc_, 0, 0, 0);         \
@@ -504,94 +427,7 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
   })
 #endif
 
-  // ---- PERSIST: the LDS-DMA ring of this unit ---------------------------------------------------------------------
-  // fragment read offsets (halves) inside a stage: K row l31, logical piece P(plane, st) at P ^ swizzle(row); V row
-  // 4 h + rr (+ 16 t + 8 a as an immediate), piece Pv(plane, dt) ^ swizzle(row), the lane's 8-byte half of it
-  const unsigned short *ring = lds + gw * NSTG * STAGE_H;
-  int koffs[2][4], voffs[2][2];
-  {
-    const int swk = PLAIN ? ((l31 >> 1) & 7) : (l31 & 15);
-    const int rr = (lane & 15) >> 2, b_ = (lane >> 4) & 1, c_ = lane & 3;
-    const int swv = PLAIN ? 4 * (rr >> 1) : 4 * rr;
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-#pragma unroll
-      for (int st = 0; st < 4; ++st) {
-        const int P = PLAIN ? 2 * st + h : 8 * (st >> 1) + 4 * pl + 2 * (st & 1) + h;
-        koffs[pl][st] = l31 * ROWH + ((P ^ swk) << 3);
-      }
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const int Pv = PLAIN ? 4 * dt + 2 * b_ + (c_ >> 1) : 8 * dt + 4 * pl + 2 * b_ + (c_ >> 1);
-        voffs[pl][dt] = KIMG + (4 * h + rr) * ROWH + ((Pv ^ swv) << 3) + 4 * (c_ & 1);
-      }
-    }
-  }
-  // DMA instruction q = wave + NW n of a stage: wave group q / NIG, K (first half) or V, rows RPI i .. of the tile; lane l
-  // fetches the logical piece that belongs into physical slot l % PPR of row l / PPR.  dq_*: what stays fixed for the unit.
-  const int wave_s = PERSIST ? __builtin_amdgcn_readfirstlane(wave) : 0;
-  const int ni_unit = (PERSIST && split) ? 2 * NIG : NIG;
-  int dq_row[NPW], dq_tile[NPW], n_w = 0;
-  unsigned dq_col[NPW], dq_dst[NPW];
-  if (PERSIST) {
-    const unsigned lds_b = (unsigned)(size_t)((__attribute__((address_space(3))) unsigned short *)lds);
-#pragma unroll
-    for (int n = 0; n < NPW; ++n) {
-      const int q = wave_s + NW * n;
-      const int grp = q / NIG, qq = q - grp * NIG;
-      const int isv = qq >= NIG / 2 ? 1 : 0, i_ = qq - isv * (NIG / 2);
-      const int r_ = RPI * i_ + lane / PPR, pp = lane % PPR;
-      const int sw = isv ? (PLAIN ? 4 * ((r_ >> 1) & 1) : 4 * (r_ & 3)) : (PLAIN ? ((r_ >> 1) & 7) : (r_ & 15));
-      dq_row[n] = r_;
-      dq_tile[n] = grp * (j1 - j0);
-      dq_col[n] = (unsigned)((isv ? voff : koff) * 2) + (unsigned)((pp ^ sw) * 16);
-      dq_dst[n] = lds_b + (unsigned)((grp * NSTG * STAGE_H + isv * KIMG) * 2 + i_ * 1024);
-      n_w += (q < ni_unit) ? 1 : 0;
-    }
-  }
-#if defined(__HIP_DEVICE_COMPILE__)
-#define CRA5_DMA_ISSUE(T)                                                                 \
-  {                                                                                       \
-    const int jj_ = min((T), n_tiles - 1);                                                \
-    const unsigned slot_ = (unsigned)(((T) & (NSTG - 1)) * STAGE_H * 2);                  \
-    _Pragma("unroll") for (int n = 0; n < NPW; ++n) {                                     \
-      if (wave_s + NW * n < ni_unit) {                                                    \
-        const char *src_ = reinterpret_cast<const char *>(qkv) + tab[(jj_ + dq_tile[n]) * 32 + dq_row[n]] + dq_col[n]; \
-        const unsigned dst_ = dq_dst[n] + slot_;                                          \
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"   \
-                     :: "s"(dst_), "v"(src_) : "memory", "m0");                           \
-      }                                                                                   \
-    }                                                                                     \
-  }
-  // own DMA instructions of the stages before the newest one have landed (vmcnt counts in issue order); LATER = 0: all
-#define CRA5_DMA_WAIT(LATER)                                                              \
-  {                                                                                       \
-    const int k_ = (LATER) ? n_w : 0;                                                     \
-    if (k_ == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         \
-    else if (k_ == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");                    \
-    else if (k_ == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                    \
-    else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");                                 \
-  }
-#else
-#define CRA5_DMA_ISSUE(T) (void)dq_row, (void)dq_tile, (void)dq_col, (void)dq_dst
-#define CRA5_DMA_WAIT(LATER) (void)n_w
-#endif
-  static_assert(!PERSIST || NPW <= 3, "CRA5_DMA_WAIT is written out for at most three instructions per wave and stage");
-
   f32x16 s_cur;
-  float mloc;
-  if (PERSIST) {
-    // prologue: stages 0, 1, 2 requested (every wave is past the barrier that published this unit's row table and has
-    // drained its own DMAs / stores of the previous unit); stages 0 and 1 must have landed before the first scores
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    CRA5_DMA_ISSUE(0);
-    if (n_tiles > 1) CRA5_DMA_ISSUE(1);
-    if (n_tiles > 2) CRA5_DMA_ISSUE(2);
-    CRA5_DMA_WAIT(n_tiles > 2);
-    __syncthreads();
-    CRA5_SCORES(s_cur, 0);
-    mloc = CRA5_TILE_MAX(s_cur);
-  } else {
   // prologue: K(0), V(0), K(1) resident; K(2), V(1) in flight; S(0) done
   CRA5_K_LOAD(0);
   CRA5_V_LOAD(0);
@@ -603,21 +439,17 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
   CRA5_K_LOAD(2);
   CRA5_V_LOAD(1);
   CRA5_SCORES(s_cur, 0);
-  mloc = CRA5_TILE_MAX(s_cur);
+  float mloc = CRA5_TILE_MAX(s_cur);
   // The end of iteration 0 re-fills K buffer 0 with tile 2: every wave must be done reading tile 0 from
   // it (a wave a whole iteration ahead of another is unlikely, not impossible).
   __syncthreads();
-  }
 
   // Waves past the end of the window (q_tok < 0 for all lanes) run the same instruction stream
   // on the pad row and store nothing: one code path, no divergent barriers.
   // One key tile; the loop below is unrolled by two with the score registers swapping roles, so that tile j+1's
   // scores never have to be copied into tile j's registers (8 v_mov_b64 per tile).
   auto key_tile = [&](const int j, f32x16 &s_cur, f32x16 &s_next) __attribute__((always_inline)) {
-    const int kb = PERSIST ? ((j + 1) & (NSTG - 1)) : ((j + 1) & 1), vb = PERSIST ? (j & (NSTG - 1)) : (j & 1);
-    // PERSIST: stage j + 3 goes into the slot stage j - 1 left at the last barrier (nothing is requested past the unit's
-    // last tile: the tail waits for everything instead)
-    if (PERSIST && j + 3 < n_tiles) CRA5_DMA_ISSUE(j + 3);
+    const int kb = (j + 1) & 1, vb = j & 1;
     // (a wave whose 32 queries all lie past the end of the window - half of the fifth 128-query work-group of a
     // 576-token window - only stages and synchronises: its MFMAs would be taken from the other waves of its SIMD)
     if (!IDLE_SKIP || wave_active) {
@@ -773,12 +605,12 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
       half8 vh[2], vl[2];
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        const unsigned short *vp = PERSIST ? ring + vb * STAGE_H + voffs[0][dt] + 16 * t * ROWH : v_base + vb * VBUF + 16 * t * VS + 32 * dt;
-        const unsigned short *vq = PERSIST ? ring + vb * STAGE_H + voffs[PLAIN ? 0 : 1][dt] + 16 * t * ROWH : vp + VPL;
+        const unsigned short *vp = v_base + vb * VBUF + 16 * t * VS + 32 * dt;
+        const unsigned short *vq = vp + VPL;
         const half4 a0 = CRA5_TR_READ(vp);
-        const half4 a1 = CRA5_TR_READ(vp + 8 * (PERSIST ? ROWH : VS));
+        const half4 a1 = CRA5_TR_READ(vp + 8 * VS);
         const half4 b0 = CRA5_TR_READ(vq);
-        const half4 b1 = CRA5_TR_READ(vq + 8 * (PERSIST ? ROWH : VS));
+        const half4 b1 = CRA5_TR_READ(vq + 8 * VS);
         vh[dt] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
         vl[dt] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
       }
@@ -796,16 +628,10 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
     // K(j+2) -> the buffer tile j's scores came from (last read before the previous barrier),
     // V(j+1) -> the other V buffer (past the end: stale data into buffers nobody reads);
     // then start fetching K(j+3), V(j+2).
-    if (PERSIST) {
-      // stage j + 2 (the K tile of the next step's scores) was requested two steps ago: this wave's share of it has
-      // landed once at most its share of stage j + 3 - requested at the top of this step, if at all - is outstanding
-      CRA5_DMA_WAIT(j + 3 < n_tiles);
-    } else {
     CRA5_K_STORE(j & 1);
     CRA5_V_STORE((j + 1) & 1);
     CRA5_K_LOAD(j + 3);
     CRA5_V_LOAD(j + 2);
-    }
     __syncthreads();
   };
   CRA5_ATRACE(1, wall_clock64());
@@ -818,44 +644,10 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
   }
   if (jt < n_loop) key_tile(jt, s_cur, s_alt);
   CRA5_ATRACE(2, wall_clock64());
-  CRA5_ATRACE(4, (unsigned long long)n_tiles + ((PERSIST && split) ? 1000 : 0));
+  CRA5_ATRACE(4, (unsigned long long)n_tiles);
 
-  if (PERSIST && split) {
-    // merge of the two key halves of a SPLIT unit: wave group 1 parks (m, l) and its 32 accumulator registers in the K / V
-    // area (after the key loop's last barrier nobody reads it), 16 registers per round; group 0 combines them with its
-    // own - first key half first, fixed association - and stores.  [wq][register][lane] floats: conflict-free.
-    float *scr = reinterpret_cast<float *>(lds);
-    float ma = 1.f, mb = 1.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      if (gw == 1) {
-        float *dst = scr + (size_t)wq * 18 * 64 + lane;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dst[r * 64] = o[t][r];
-        if (t == 0) {
-          dst[16 * 64] = m_run;
-          dst[17 * 64] = l_run;
-        }
-      }
-      __syncthreads();
-      if (gw == 0) {
-        const float *src = scr + (size_t)wq * 18 * 64 + lane;
-        if (t == 0) {
-          const float m_b = src[16 * 64], l_b = src[17 * 64];
-          const float M = fmaxf(m_run, m_b);
-          ma = __builtin_amdgcn_exp2f(m_run - M);
-          mb = __builtin_amdgcn_exp2f(m_b - M);
-          l_run = fmaf(l_b, mb, l_run * ma);
-          m_run = M;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[t][r] = fmaf(src[r * 64], mb, o[t][r] * ma);
-      }
-      __syncthreads();
-    }
-  }
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  if (BAL && seg_part[PERSIST ? 0 : seg] >= 0) {
+  if (BAL && seg_part[seg] >= 0) {
     // un-normalised partial of this key range: O, running max (log2 domain), sum - merged by attention_merge_kernel
     if (q_tok >= 0) {
       float *wrow = bal.ws + (((((size_t)head * bal.n_grp + seg_grp[seg]) * bal.maxp + seg_part[seg]) * NW + wave) * 32 + l31) * WS_ROW;
@@ -879,7 +671,7 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
   // v_permlane32_swap per dword turns the groups (g, g + 1) of the two half-waves into 16 contiguous bytes per lane:
   // lanes 0-31 get columns 16 p .. 16 p + 7 of the pair, lanes 32-63 the next eight (8 sixteen-byte stores per lane).
   {
-    const bool live = q_tok >= 0 && gw == 0;        // (SPLIT units: wave group 0 holds the merged result)
+    const bool live = q_tok >= 0;
     const float inv = live ? 1.0f / l_tot : 0.0f;   // (dead lanes take part in the swaps below: keep their values finite)
     float *orow = (out && live) ? out + (size_t)q_tok * C + hoff : nullptr;
     unsigned short *srow = (out_s && live) ? out_s + (size_t)q_tok * 2 * Kp_out : nullptr;
@@ -1068,25 +860,6 @@ int launch(const unsigned short *qkv, long ldq, const unsigned short *pad_row, f
   return (int)hipGetLastError();
 }
 
-// Windowed launch as persistent 12-wave work-groups walking (window, head) units (PERSIST above): one work-group per CU.
-template <bool HI, bool PLAIN = false>
-int launch_persist(const unsigned short *qkv, long ldq, const unsigned short *pad_row, float *out, unsigned short *out_s,
-                   int Kp_out, int C, int heads, int H, int W, int wh, int ww, float scale, hipStream_t st) {
-  WinGeom g;
-  g.H = H;
-  g.W = W;
-  g.wh = wh;
-  g.ww = ww;
-  const int nwr = (H + wh - 1) / wh;
-  g.nwc = (W + ww - 1) / ww;
-  const int T = (wh * ww) / 32, pairs = nwr * g.nwc * heads;
-  const int units = pairs * (T / NW_GLOBAL + (T % NW_GLOBAL ? 1 : 0));
-  const int grid = units < cu_count() ? units : cu_count();
-  hipLaunchKernelGGL((window_attention_split_kernel<NW_GLOBAL, HI, false, false, PLAIN, true>), dim3(grid), dim3(NW_GLOBAL * 64),
-                     0, st, qkv, ldq, pad_row, out, out_s, Kp_out, C, heads, g, nwr * g.nwc, scale, BalArgs{});
-  return (int)hipGetLastError();
-}
-
 }  // namespace
 
 static int attention_dispatch(const uint16_t *qkv_split, int qkv_kp, const uint16_t *pad_row_split, float *out,
@@ -1101,13 +874,7 @@ static int attention_dispatch(const uint16_t *qkv_split, int qkv_kp, const uint1
   hipStream_t st = (hipStream_t)stream;
   const int L = wh * ww;
   // hi_only: 0 = fp32-accurate, 1 = reduced precision on split rows, 3 = reduced precision on PLAIN f16 rows (qkv, the
-  // pad row and out_split: element n at half n; row pitches unchanged); + CRA5_ATTN_PERSISTENT_UNITS (4): windowed
-  // launches as persistent 12-wave units.  The 4-wave work-groups of rounds 2-5 (three per CU) stay the default: the unit
-  // walk is built, tested and SLOWER - 117 vs 92 us on the model's 24 x 24 windows (profiles/r06_attn_window_ab.txt): with
-  // one work-group per CU nothing runs under a unit's prologue / epilogue (three independent 4-wave work-groups stagger
-  // themselves), and a 12-wave barrier domain steps in 2.8 us where the three small ones average 2.2.
-  const bool persistent_units = (hi_only & CRA5_ATTN_PERSISTENT_UNITS) != 0;
-  hi_only &= ~CRA5_ATTN_PERSISTENT_UNITS;
+  // pad row and out_split: element n at half n; row pitches unchanged).
   if (hi_only != 0 && hi_only != 1 && hi_only != 3) return CRA5_ERR_ARG;
   const bool plain = hi_only == 3;
   const long ldq = 2L * qkv_kp;
@@ -1136,12 +903,10 @@ static int attention_dispatch(const uint16_t *qkv_split, int qkv_kp, const uint1
   // window, K / V staged three times instead of five) looks better on paper and ran with ONE work-group per CU: its
   // waves land on the SIMDs 2-2-1-1, a second work-group would put four 156-register waves on one SIMD (3 fit), so
   // 864 work-groups took 3.4 rounds instead of 1.7.  Four waves are one per SIMD: three work-groups always fit.
-  // (opt-in, round 6: windows of >= 12 wave-tiles as persistent 12-wave units - see windows_persistent())
-  if (L / 32 >= NW_GLOBAL && persistent_units) {
-    if (plain) return launch_persist<true, true>(qkv_split, ldq, pad_row_split, out, out_split, out_kp, C, heads, H, W, wh, ww, scale, st);
-    if (hi_only) return launch_persist<true>(qkv_split, ldq, pad_row_split, out, out_split, out_kp, C, heads, H, W, wh, ww, scale, st);
-    return launch_persist<false>(qkv_split, ldq, pad_row_split, out, out_split, out_kp, C, heads, H, W, wh, ww, scale, st);
-  }
+  // Persistent 12-wave work-groups walking (window, head) units (round 6) were SLOWER - 117 vs 92 us on the model's
+  // 24 x 24 windows: with one work-group per CU nothing runs under a unit's prologue / epilogue (three independent 4-wave
+  // work-groups stagger themselves), and a 12-wave barrier domain steps in 2.8 us where the three small ones average 2.2
+  // (profiles/EXPERIMENTS.md).
   if (plain) return launch<4, true, false, true>(qkv_split, ldq, pad_row_split, out, out_split, out_kp, C, heads, H, W, wh, ww, scale, st);
   if (hi_only) CRA5_ATT_GO(4, true, false);
   CRA5_ATT_GO(4, false, false);

@@ -119,8 +119,8 @@ struct UnembedArgs {
   int H, W, Hp, Wp;
 };
 
-template <int WM, int WN, int TM, int TN, bool LONGK, int STAGES = 2, int NPROD = 3, bool UE = false>
-__global__ __launch_bounds__(WM *WN * 64, ((STAGES == 1 || (WM * WN == 4 && TM == 3)) ? 2 : 1)) void gemm_nt_split_kernel(
+template <int WM, int WN, int TM, int TN, bool LONGK, int NPROD = 3, bool UE = false>
+__global__ __launch_bounds__(WM *WN * 64, ((WM * WN == 4 && TM == 3) ? 2 : 1)) void gemm_nt_split_kernel(
     const unsigned short *__restrict__ A, long lda, const unsigned short *__restrict__ W, long ldw, float *C,
     int ldc, unsigned short *Cs, long ldcs, const float *__restrict__ bias, const float *res, int ldr, int M,
     int N, int Kp, float wscale_inv, int flags, int tiles_n, UnembedArgs ue) {
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(WM *WN * 64, ((STAGES == 1 || (WM * WN == 4 && TM =
 
   // two stages of [A rows][W rows], 128 B per row = [32 hi | 32 lo] of one k-step, XOR-swizzled in
   // 16-byte pieces (see the staging comment below); 2 x (BM + BN) x 128 B, no padding.
-  __shared__ __attribute__((aligned(16))) unsigned short lds[STAGES * STAGE];
+  __shared__ __attribute__((aligned(16))) unsigned short lds[2 * STAGE];
 
   CRA5_TRACE(0);
 #ifdef CRA5_GEMM_TRACE
@@ -520,13 +520,13 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float *__restrict
   }
 }
 
-template <int WM, int WN, int TM, int TN, bool LONGK, int STAGES = 2, int NPROD = 3, bool UE = false>
+template <int WM, int WN, int TM, int TN, bool LONGK, int NPROD = 3, bool UE = false>
 int launch(const unsigned short *A, long lda, const unsigned short *W, long ldw, float *C, int ldc,
            unsigned short *Cs, long ldcs, const float *bias, const float *res, int ldr, int M, int N, int Kp,
            float wscale_inv, int flags, hipStream_t st, UnembedArgs ue = UnembedArgs{}) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  hipLaunchKernelGGL((gemm_nt_split_kernel<WM, WN, TM, TN, LONGK, STAGES, NPROD, UE>), dim3(tiles_m * tiles_n),
+  hipLaunchKernelGGL((gemm_nt_split_kernel<WM, WN, TM, TN, LONGK, NPROD, UE>), dim3(tiles_m * tiles_n),
                      dim3(WM * WN * 64), 0, st, A, lda, W, ldw, C, ldc, Cs, ldcs, bias, res, ldr, M, N, Kp, wscale_inv,
                      flags, tiles_n, ue);
   return (int)hipGetLastError();
@@ -570,8 +570,8 @@ static int gemm_dispatch(const unsigned short *A, long lda, const unsigned short
   const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
 #define CRA5_GO(WM, WN, TM, TN, LK) \
   return launch<WM, WN, TM, TN, LK>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st)
-// variant builds only: the product library reads no environment variable
-#if defined(CRA5_TUNING_ENV) || defined(CRA5_GEMM_TRACE)
+// trace build only (tools/gemm_trace.py --active forces a tile): the product library reads no environment variable
+#ifdef CRA5_GEMM_TRACE
   static const int forced = [] {
     const char *e = getenv("CRA5_GEMM_TILE");
     return e ? atoi(e) : 0;
@@ -587,15 +587,15 @@ static int gemm_dispatch(const unsigned short *A, long lda, const unsigned short
   if (flags & CRA5_GEMM_HI_ONLY) {   // reduced precision: one f16 MFMA per product
     const bool wide = (M >= 1024 && N >= 2048);
     if (tiles128 < 256)
-      return launch<2, 2, 1, 1, false, 2, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
+      return launch<2, 2, 1, 1, false, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
     if (Kp % 64 == 0) {   // wide form: 64 k-values (the hi halves of two chunks) per k-step, the fp32-accurate mode's loop
       if (wide)
-        return launch<2, 4, 4, 2, false, 2, 2>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
-      return launch<2, 4, 3, 2, false, 2, 2>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
+        return launch<2, 4, 4, 2, false, 2>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
+      return launch<2, 4, 3, 2, false, 2>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
     }
     if (wide)
-      return launch<2, 4, 4, 2, false, 2, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
-    return launch<2, 4, 3, 2, false, 2, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
+      return launch<2, 4, 4, 2, false, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
+    return launch<2, 4, 3, 2, false, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
   }
   int tile = forced;
   if (!tile) {
@@ -705,13 +705,13 @@ extern "C" int cra5_gemm_nt_split_unembed(const uint16_t *A, int lda_kp, const u
   const long lda = a_plain ? (long)lda_kp : 2L * lda_kp, ldw = w_plain ? (long)ldw_kp : 2L * ldw_kp;
   int rc;
   if (hi_only && Kp % 64 == 0)
-    rc = launch<2, 4, 4, 2, false, 2, 2, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv,
+    rc = launch<2, 4, 4, 2, false, 2, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv,
                                                CRA5_GEMM_HI_ONLY | (a_plain ? CRA5_GEMM_A_PLAIN : 0) | (w_plain ? CRA5_GEMM_W_PLAIN : 0), st, ue);
   else if (hi_only)
-    rc = launch<2, 4, 4, 2, false, 2, 1, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv,
+    rc = launch<2, 4, 4, 2, false, 1, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv,
                                                CRA5_GEMM_HI_ONLY, st, ue);
   else
-    rc = launch<2, 4, 4, 2, false, 2, 3, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv,
+    rc = launch<2, 4, 4, 2, false, 3, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv,
                                                0, st, ue);
   if (rc) return rc;
   const size_t total = (size_t)C * (Hp + 1) * (W / 4);

@@ -396,31 +396,11 @@ extern "C" int cra5_small_gemm_nt_split(const uint16_t *A, int lda_kp, const uin
   return launch_small<TN, KS, D, false>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, ps, st)
   const long tiles1 = (long)((M + 31) / 32) * ((N + 31) / 32);
   const int nk = Kp / 32;
-  // The instantiation is a function of the SHAPE only: it fixes the split-K factor and with it the fp32 summation
-  // order of h_s, which encoder and decoder must share bit for bit.  The sweep override (CRA5_HY_GEMM = "TN KS",
-  // tools/hyper_gemm_sweep.py) exists only in -DCRA5_HY_SWEEP builds (tools/build_variant.sh), never in the product.
-#ifdef CRA5_HY_SWEEP
-  static const int forced = [] {
-    const char *e = getenv("CRA5_HY_GEMM");
-    int tn = 0, ks = 0;
-    if (e && sscanf(e, "%d %d", &tn, &ks) == 2) return tn * 100 + ks;
-    return 0;
-  }();
-  switch (forced) {
-    case 101: HY_GO(1, 1, 4);
-    case 102: HY_GO(1, 2, 4);
-    case 104: HY_GO(1, 4, 2);
-    case 108: HY_GO(1, 8, 2);
-    case 201: HY_GO(2, 1, 3);
-    case 202: HY_GO(2, 2, 2);
-    case 204: HY_GO(2, 4, 2);
-    case 401: HY_GO(4, 1, 2);
-    default: break;
-  }
-#endif
-  // Measured on MI355X.  Warm micro-benchmark per shape (tools/hyper_gemm_sweep.sh, kernel us, this kernel vs the
-  // LDS-tiled engine at a fixed 64 / 128 tile): 648x360x4096 34 vs 65, 648x360x1440 15.1 vs 16.2, 648x1080x360
-  // 13.2 vs 8.6, 648x1440x360 16.1 vs 9.1, 648x8192x360 60 vs 26.  IN SITU (every GEMM of h_s meets weights that
+  // The instantiation is a function of the SHAPE only, with no override in any build: it fixes the split-K factor and
+  // with it the fp32 summation order of h_s, which encoder and decoder must share bit for bit.
+  // Measured on MI355X.  Warm micro-benchmark per shape (kernel us, this kernel vs the LDS-tiled engine at a fixed 64 /
+  // 128 tile; the sweep: `git show d3ed7fb:tools/hyper_gemm_sweep.py`): 648x360x4096 34 vs 65, 648x360x1440 15.1 vs
+  // 16.2, 648x1080x360 13.2 vs 8.6, 648x1440x360 16.1 vs 9.1, 648x8192x360 60 vs 26.  IN SITU (every GEMM of h_s meets weights that
   // are cold in L2; tools/hyper_bench.py) the picture flips for the short reductions too - h_s 436 us with this
   // kernel everywhere vs 507 us with the 64-tile engine forwarded for K = 360: four k-steps of loads in flight
   // per wave ride out the misses that a two-stage LDS pipeline stalls on.  So: this kernel for every shape.

@@ -65,9 +65,7 @@ def test_release_sources_carry_no_experiment_switches():
                "__x86_64__",
                "CRA5_RANGE_CHECK",           # `rangecheck` flavour: counts out-of-range split-f16 stores (same results)
                "CRA5_GEMM_TRACE",            # tools/gemm_trace.py: per-work-group timestamps (same results)
-               "CRA5_ATTN_TRACE",            # tools/attn_trace.py: per-work-group / per-unit timestamps of the windowed attention
-               "CRA5_HY_SWEEP",              # tools/hyper_gemm_sweep.sh: CRA5_HY_GEMM override of the small-GEMM shape
-               "CRA5_TUNING_ENV"}            # variant builds: CRA5_GEMM_TILE / CRA5_ATT72_NW tile overrides (same results)
+               "CRA5_ATTN_TRACE"}            # tools/attn_trace.py: per-work-group timestamps of the windowed attention
     csrc = os.path.join(ROOT, "cra5_amd", "csrc")
     seen = set()
     for f in sorted(os.listdir(csrc)):
@@ -88,8 +86,8 @@ def test_release_sources_carry_no_experiment_switches():
 
 def test_product_library_reads_no_environment_variable():
     """Round 6: settings come from ONE place, cra5_amd/config.py RuntimeConfig.from_env(); the native
-    library itself imports no getenv (the tile-override hooks of earlier rounds exist in -DCRA5_TUNING_ENV variant builds
-    only) and no other module of the package reads a CRA5_* setting from os.environ."""
+    library itself imports no getenv (only the -DCRA5_GEMM_TRACE variant build reads a forced GEMM tile for
+    tools/gemm_trace.py) and no other module of the package reads a CRA5_* setting from os.environ."""
     import subprocess
     from cra5_amd import build as B
     lib = B.build()

@@ -627,7 +627,7 @@ def test_window_attention_plain_rows_equal_the_hi_only_split_launch(dev, ws):
 def test_split_attention_shape_rule(dev):
     """Windows that are not the whole grid keep a per-block row-offset table: more than
     ops.MAX_WIN_TOKENS tokens per window is refused by the C ABI (the model then uses the exact-f32
-    kernel, ops.split_attention_ok says so beforehand)."""
+    kernel, ops.split_attention_ok says so beforehand).  So is a hi_only other than 0, 1 or 3."""
     H, W, C, heads = 64, 64, 64, 1
     assert ops.split_attention_ok(C, heads, 32, 32, H, W)           # 1024-token windows: fine
     assert not ops.split_attention_ok(C, heads, 64, 32, H, W)       # 2048-token windows: no
@@ -641,6 +641,12 @@ def test_split_attention_shape_rule(dev):
     ops.window_attention_split(qkv, pad, heads, H, W, 32, 32, out_split=out)
     torch.cuda.synchronize()
     assert torch.isfinite(out.to_float()).all()
+    # hi_only is 0, 1 or 3: any other value (4 once selected a removed windowed schedule) is refused before a launch
+    from cra5_amd import _lib
+    rc = _lib.lib().cra5_window_attention_split(qkv.data.data_ptr(), qkv.Kp, pad.data.data_ptr(), None,
+                                                out.data.data_ptr(), out.Kp, C, heads, H, W, 32, 32, 0.125, 4,
+                                                torch.cuda.current_stream().cuda_stream)
+    assert rc == -7   # CRA5_ERR_ARG
 
 
 def test_split_f16_range_guard(dev):
@@ -880,38 +886,3 @@ def test_global_attention_balanced_schedule_random_shapes(dev):
         if done >= 12:
             break
     assert done >= 6
-
-
-def test_window_attention_persistent_units_opt_in(dev):
-    """Round 6 experiment kept as an opt-in flag of the C ABI (CRA5_ATTN_PERSISTENT_UNITS): windowed launches as persistent
-    12-wave work-groups walking (window, head) units, the six left-over wave-tiles of a 576-token window run as a key-SPLIT
-    unit whose two halves are merged through LDS.  Same bounds as the product path: fp32-accurate form against float64 at the
-    exact-f32 kernel's accuracy class on the three window shapes (48 x 12: padded windows); tokens of FULL units are
-    bit-identical to the default schedule (same arithmetic), the others differ by fp32 rounding; both reduced-precision
-    layouts stay in their class."""
-    H, W, C, heads = 72, 144, 128, 2
-    g = torch.Generator().manual_seed(11)
-    x = torch.randn(1, H * W, C, generator=g)
-    sd = synth.fill_state_dict({"attn.qkv.weight": (3 * C, C), "attn.qkv.bias": (3 * C,), "attn.proj.weight": (C, C),
-                                "attn.proj.bias": (C,)}, seed=21)
-    sd["attn.qkv.weight"] *= 3.0
-    xd = {k: v.double() for k, v in sd.items()}
-    xs = ops.split_f16(x[0].to(dev))
-    qkv_s = ops.SplitMat.empty(H * W, 3 * C, dev)
-    ops.gemm_nt_split(xs, ops.split_f16(sd["attn.qkv.weight"].to(dev), "auto"), bias=sd["attn.qkv.bias"].to(dev),
-                      out_split=qkv_s, want_f32=False)
-    pad_s = ops.split_f16(sd["attn.qkv.bias"].to(dev).reshape(1, -1))
-    for ws in ((24, 24), (12, 48), (48, 12)):
-        ref = R.attention_window(x.double(), xd, "attn", heads, H, W, ws)
-        att = ops.SplitMat.empty(H * W, C, dev, zero=True)
-        o_p = torch.empty(H * W, C, device=dev)
-        ops.window_attention_split(qkv_s, pad_s, heads, H, W, ws[0], ws[1], out=o_p, out_split=att, persistent_units=True)
-        out = ops.gemm_nt_split(att, ops.split_f16(sd["attn.proj.weight"].to(dev), "auto"), bias=sd["attn.proj.bias"].to(dev))
-        assert rmse(out, ref[0]) < 4e-6                      # the product path's bound (test_window_attention_split_f16)
-        o_c = torch.empty(H * W, C, device=dev)
-        ops.window_attention_split(qkv_s, pad_s, heads, H, W, ws[0], ws[1], out=o_c)
-        same = float((o_p == o_c).float().mean())
-        assert same >= 0.6 and float((o_p - o_c).abs().max()) < 1e-5, (ws, same)   # 12 of 18 wave-tiles per window run FULL units
-        o16 = torch.empty(H * W, C, device=dev)
-        ops.window_attention_split(qkv_s, pad_s, heads, H, W, ws[0], ws[1], out=o16, hi_only=True, persistent_units=True)
-        assert torch.isfinite(o16).all() and rmse(o16, o_c) < 2e-3 * float(o_c.double().pow(2).mean().sqrt())

@@ -34,4 +34,4 @@ for _ in range(3): ops.window_attention(qkv2, b2, h2, H2, W2, H2, W2, out=o2)
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(50): ops.window_attention(qkv2, b2, h2, H2, W2, H2, W2, out=o2)
 torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 50
-print(f"f32 hyper 648x72 : {dt*1e6:8.1f} us (CRA5_ATT72_NW={os.environ.get('CRA5_ATT72_NW','auto')})", flush=True)
+print(f"f32 hyper 648x72 : {dt*1e6:8.1f} us", flush=True)
