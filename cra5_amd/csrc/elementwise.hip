@@ -464,7 +464,10 @@ __global__ __launch_bounds__(256) void unary_kernel(const float *__restrict__ x,
                                                     float slope) {
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
     const float v = x[e];
-    y[e] = (op == 1) ? __builtin_fabsf(v) : ((v >= 0.f) ? v : v * slope);   // 0: relu / leaky relu, 1: abs
+    // torch's own definitions, bit for bit: leaky_relu = v > 0 ? v : v * slope (slope honoured, 0 included);
+    // relu = v < 0 ? 0 : v (relu(-inf) = +0, relu(-0) = -0, NaN passes) - never v * 0, which is NaN at -inf
+    // and -0 for every negative v
+    y[e] = (op == 1) ? __builtin_fabsf(v) : (op == 2) ? ((v < 0.f) ? 0.f : v) : ((v > 0.f) ? v : v * slope);
   }
 }
 
@@ -811,7 +814,7 @@ int cra5_deconv_col2im_f32(const float *cols, const float *bias, float *out, int
 }
 
 int cra5_unary_f32(const float *x, float *y, size_t n, int op, float slope, void *stream) {
-  if (!x || !y || n == 0 || op < 0 || op > 1) return CRA5_ERR_ARG;
+  if (!x || !y || n == 0 || op < 0 || op > 2) return CRA5_ERR_ARG;
   hipLaunchKernelGGL(unary_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, y, n, op, slope);
   return (int)hipGetLastError();
 }

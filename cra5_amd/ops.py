@@ -643,12 +643,12 @@ def conv_transpose2d(x, w_split, bias, cout, k, stride):
     return out
 
 
-def unary(x, op, slope=0.0):
-    """op: 'relu' | 'leaky_relu' (slope) | 'abs'."""
+def unary(x, op, slope=0.01):
+    """op: 'relu' | 'leaky_relu' (negative slope `slope`, torch's default 0.01; 0.0 is honoured) | 'abs'."""
     _dev(x)
     x = x.contiguous()
     y = torch.empty_like(x)
-    code, sl = {"relu": (0, 0.0), "leaky_relu": (0, slope or 0.01), "abs": (1, 0.0)}[op]
+    code, sl = {"relu": (2, 0.0), "leaky_relu": (0, slope), "abs": (1, 0.0)}[op]
     check(lib().cra5_unary_f32(_p(x), _p(y), x.numel(), code, float(sl), _stream()), "cra5_unary_f32")
     return y
 

@@ -286,7 +286,8 @@ int cra5_conv_im2col_f32(const float *x, uint16_t *cols_split, int C, int H, int
                          int ph, int pw, int Ho, int Wo, int ldk, void *stream);
 int cra5_deconv_col2im_f32(const float *cols, const float *bias, float *out, int Cout, int Hi, int Wi, int kh, int kw,
                            int sh, int sw, int ph, int pw, int Ho, int Wo, int ldn, void *stream);
-/* y = relu(x) / leaky_relu(x, slope) (op 0; slope 0 = ReLU) or |x| (op 1); x == y allowed. */
+/* y = leaky_relu(x, slope) (op 0, any slope), |x| (op 1) or relu(x) (op 2), each bit-identical to torch's;
+ * x == y allowed. */
 int cra5_unary_f32(const float *x, float *y, size_t n, int op, float slope, void *stream);
 
 /* ============================ device: entropy models ========================== */

@@ -425,3 +425,66 @@ def gdn(x, beta_param, gamma_param, inverse=False, beta_min=1e-6, reparam_offset
     norm = F.conv2d(x ** 2, gamma.reshape(C, C, 1, 1), beta)
     norm = torch.sqrt(norm) if inverse else torch.rsqrt(norm)
     return x * norm
+
+
+# ----------------------------------------------------------------------------
+# CNN zoo codecs (bmshj2018-factorized / -factorized-relu / -hyperprior, mbt2018-mean)
+# ----------------------------------------------------------------------------
+# Layer lists of models/google.py:64-508 with models/utils.py:128-146:
+#   "c5" conv 5x5 stride 2, "c3" conv 3x3 stride 1 (both padding k//2),
+#   "d5" deconv 5x5 stride 2 (padding 2, output_padding 1), "gdn" / "igdn" GDN / inverse GDN,
+#   "relu", "lrelu" LeakyReLU(0.01).  Entry i of a list is module i of the nn.Sequential
+#   (state-dict prefix "<net>.<i>").
+
+_CNN_G = {
+    "gdn": dict(g_a=["c5", "gdn", "c5", "gdn", "c5", "gdn", "c5"],
+                g_s=["d5", "igdn", "d5", "igdn", "d5", "igdn", "d5"]),
+    "relu": dict(g_a=["c5", "relu", "c5", "relu", "c5", "relu", "c5"],
+                 g_s=["d5", "relu", "d5", "relu", "d5", "relu", "d5"]),
+}
+CNN_LAYERS = {
+    "factorized": dict(_CNN_G["gdn"]),
+    "factorized_relu": dict(_CNN_G["relu"]),
+    "hyperprior": dict(_CNN_G["gdn"], h_a=["c3", "relu", "c5", "relu", "c5"],
+                       h_s=["d5", "relu", "d5", "relu", "c3", "relu"]),
+    "meanscale": dict(_CNN_G["gdn"], h_a=["c3", "lrelu", "c5", "lrelu", "c5"],
+                      h_s=["d5", "lrelu", "d5", "lrelu", "c3"]),
+}
+
+
+def cnn_net(x, sd, arch, net):
+    """Run sub-network `net` ("g_a", "g_s", "h_a", "h_s") of `arch` (a CNN_LAYERS key) on NCHW x, in x's dtype."""
+    for i, op in enumerate(CNN_LAYERS[arch][net]):
+        pre = f"{net}.{i}"
+        if op in ("c5", "c3"):
+            k, s = (5, 2) if op == "c5" else (3, 1)
+            x = F.conv2d(x, sd[pre + ".weight"], sd[pre + ".bias"], stride=s, padding=k // 2)
+        elif op == "d5":
+            x = F.conv_transpose2d(x, sd[pre + ".weight"], sd[pre + ".bias"], stride=2, padding=2, output_padding=1)
+        elif op in ("gdn", "igdn"):
+            x = gdn(x, sd[pre + ".beta"], sd[pre + ".gamma"], inverse=op == "igdn")
+        elif op == "relu":
+            x = F.relu(x)
+        elif op == "lrelu":
+            x = F.leaky_relu(x, 0.01)
+        else:
+            raise ValueError(op)
+    return x
+
+
+def cnn_g_a(x, sd, arch):
+    return cnn_net(x, sd, arch, "g_a")
+
+
+def cnn_g_s(y_hat, sd, arch):
+    return cnn_net(y_hat, sd, arch, "g_s")
+
+
+def cnn_h_a(y, sd, arch):
+    """h_a on y itself: the caller applies the |y| of ScaleHyperprior (google.py:347) where it belongs."""
+    return cnn_net(y, sd, arch, "h_a")
+
+
+def cnn_h_s(z_hat, sd, arch):
+    """h_s: scales (hyperprior) or [scales | means] along the channels (mean-scale, chunk(2, 1))."""
+    return cnn_net(z_hat, sd, arch, "h_s")

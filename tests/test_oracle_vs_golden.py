@@ -173,3 +173,38 @@ def test_fp32_noise_floor_calibration(golden_dir):
         e_h = rmse(a["hs_synth_sub"], b["hs_synth_sub"])
         print(f"{name}: reference fp32 vs fp64: y {e_y:.2e}, hs {e_h:.2e}, x_hat {e_x:.2e}")
         assert e_y < 5e-5 and e_x < 5e-5
+
+
+def _rel(a, b):
+    a = torch.as_tensor(a).double().reshape(-1)
+    b = torch.as_tensor(b).double().reshape(-1)
+    return float(torch.sqrt(torch.mean((a - b) ** 2)) / torch.sqrt(torch.mean(b ** 2)))
+
+
+@pytest.mark.parametrize("arch", ["factorized", "factorized_relu", "hyperprior", "meanscale"])
+def test_cnn_oracle_matches_reference(golden_dir, arch):
+    """The float64 CNN codec restatement (torch_ref.cnn_*) against the reference classes' fp32 outputs
+    (cnn_zoo.npz / cnn_relu.npz, make_golden.py --stage cnn / cnn_relu), stage by stage: every stage gets the
+    reference's own input, so a round() flip cannot carry from one stage to the next."""
+    if arch == "factorized_relu":
+        g = {f"{arch}_{k}": v for k, v in np.load(f"{golden_dir}/cnn_relu.npz").items()}
+    else:
+        g = dict(np.load(f"{golden_dir}/cnn_zoo.npz").items())
+    keys = json.load(open(f"{golden_dir}/state_keys.json"))["cnn"][arch]
+    sd32 = synth.fill_state_dict({k: tuple(v) for k, v in keys.items()}, seed=11)
+    sd = {k: v.double() for k, v in sd32.items()}
+    x = torch.from_numpy(np.load(f"{golden_dir}/cnn_zoo.npz")["x"]).double()
+    with torch.no_grad():
+        y = R.cnn_g_a(x, sd, arch)
+        assert _rel(y, g[f"{arch}_y"]) <= 1e-5
+        gy = torch.Generator().manual_seed(5)
+        y_hat = torch.round(3.0 * torch.randn(y.shape, generator=gy)).double()       # the golden's decoder input
+        assert _rel(sub(R.cnn_g_s(y_hat, sd, arch), 5), g[f"{arch}_xhat_synth"]) <= 1e-5
+        if "h_a" not in R.CNN_LAYERS[arch]:
+            return
+        y_ref = torch.from_numpy(g[f"{arch}_y"]).double()
+        z = R.cnn_h_a(y_ref if arch == "meanscale" else y_ref.abs(), sd, arch)
+        assert _rel(z, g[f"{arch}_z"]) <= 1e-5
+        # h_s(entropy_bottleneck(z)): z_hat rebuilt in fp32 from the reference's own z, as the reference did
+        z_hat, _ = R.eb_forward(torch.from_numpy(g[f"{arch}_z"]), sd32)
+        assert _rel(R.cnn_h_s(z_hat.double(), sd, arch), g[f"{arch}_hs"]) <= 1e-5
