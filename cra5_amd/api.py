@@ -394,6 +394,11 @@ class cra5_api:
 
     def _encode_one(self, ts, arr, save_root, write=True):
         """One frame of the batch encode on the calling frame thread (its stream, its pinned / device buffers)."""
+        return self._encode_staged(ts, arr, save_root, write)[0]
+
+    def _encode_staged(self, ts, arr, save_root, write=True):
+        """_encode_one -> (its dict, the frame on the device: this thread's staged copy, which the compress path only
+        reads)."""
         t0 = time.time()
         if arr is None:
             arr = self.read_data_from_nc(ts)
@@ -420,7 +425,7 @@ class cra5_api:
             with Path(file_url).open("wb") as f:
                 binfmt.write_bin(f, output["strings"], output["z_shape"])
         return dict(output=output, reading_time=t1 - t0, encoding_time=t2 - t1, saving_time=time.time() - t2,
-                    save_path=file_url)
+                    save_path=file_url), x
 
     def encode_era5_batch(self, time_stamps, data=None, save_root=None, workers=12, write=True):
         """encode_era5_as_bin for many time stamps (`data`: matching list of host arrays, or None to read
@@ -513,6 +518,64 @@ class cra5_api:
 
         return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink),
                                            list(enumerate(paths)))
+
+    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights):
+        """One frame of evaluate_batch on the calling frame thread: the truth is staged once into this thread's device
+        frame buffer; the reconstruction comes from the in-memory strings (bin_path None) or from `bin_path`, and only
+        the per-channel statistics leave the device."""
+        from . import metrics
+        if bin_path is None:
+            enc, x = self._encode_staged(ts, arr, save_root, write=save_root is not None)
+            strings, shape = enc["output"]["strings"], enc["output"]["z_shape"]
+            n_bytes = 12 + sum(4 + len(s[0]) for s in strings)     # the .bin container (binfmt.write_bin)
+        else:
+            if arr is None:
+                arr = self.read_data_from_nc(ts)
+            with open(bin_path, "rb") as f:
+                blob = f.read()
+            strings, shape = binfmt.unpack_bin(blob)
+            n_bytes = len(blob)
+            with torch.no_grad():
+                x = self._stage_in(arr)      # (a truth with masked / non-finite values is reported, not refused)
+        with torch.no_grad():
+            t_d = time.perf_counter()
+            x_hat = self.net._decompress_frame(strings[0][0], strings[1][0], shape, True,
+                                               mean=self._mean_flat, std=self._std_flat)
+            self._log("decompress", t_d)
+            t_m = time.perf_counter()
+            C, H, W = x.shape[-3:]
+            if tuple(x_hat.shape[-3:]) != (C, H, W):
+                raise ValueError(f"{ts}: the reconstruction is {tuple(x_hat.shape[-3:])}, the truth frame {(C, H, W)}")
+            err = metrics.reconstruction_error(x_hat.reshape(C, H, W), x.reshape(C, H, W), lat_weights=lat_weights)
+            self._log("metrics", t_m)
+        std = self._std_flat.detach().cpu().numpy().astype(np.float64)
+        rep = dict(time_stamp=ts, variables=[self.channels_to_vname.get(c, str(c)) for c in range(C)])
+        rep.update(err)
+        rep["rmse_norm"] = err["rmse"] / std
+        rep["bin_bytes"] = n_bytes
+        rep["compression_ratio"] = C * H * W * 4 / n_bytes
+        return rep
+
+    def evaluate_batch(self, time_stamps, data=None, bins=None, save_root=None, workers=12, lat_weights="era5"):
+        """Per-variable reconstruction error of many frames, through the frame pipeline, without copying any
+        reconstruction to the host.  Truth frames: `data` (a matching list of host arrays / tensors, physical units) or
+        the NetCDF files of `time_stamps`.
+          bins=None: codec error - every frame is compressed and decompressed from the in-memory strings; the .bin is
+            written to {save_root}/{yyyy}/{ts}.bin (the bytes encode_era5_as_bin writes) only when save_root is given.
+          bins=[paths]: dataset check - the existing .bin files (e.g. downloaded CRA5 files) are decoded and compared with
+            the matching truth frames (a truth frame with NaN / inf is reported through `nonfinite`, not refused).
+        Returns one dict per frame: time_stamp, variables (channel names), the statistics of
+        metrics.reconstruction_error (float64 [C] arrays in physical units; nonfinite int64 [C]), rmse_norm = rmse / std
+        (the codec's per-channel normalisation std), bin_bytes (the container size, header included) and
+        compression_ratio = C * H * W * 4 / bin_bytes."""
+        self.net._require_gpu()
+        n = len(time_stamps)
+        frames = list(data) if data is not None else [None] * n
+        if len(frames) != n or (bins is not None and len(bins) != n):
+            raise ValueError("evaluate_batch: time_stamps, data and bins must have the same length")
+        paths = list(bins) if bins is not None else [None] * n
+        return self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights),
+                                           list(zip(time_stamps, frames, paths)))
 
     # ------------------------------------------------------------------ decode
     def _read_bin(self, bin_path):

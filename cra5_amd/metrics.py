@@ -1,4 +1,4 @@
-"""Rate estimate from the entropy models' likelihoods.
+"""Rate estimate from the entropy models' likelihoods, and the per-variable reconstruction error of a frame.
 
 `estimated_bits(out)` / `estimated_bpp(out, num_pixels)` follow the rate term of the reference's
 RateDistortionLoss (losses/rate_distortion.py:71-74): sum over the likelihood tensors of
@@ -9,6 +9,7 @@ CDF tables are charged the likelihood floor of 1e-9 = 30 bits by the estimate bu
 """
 import math
 
+import numpy as np
 import torch
 
 
@@ -21,3 +22,66 @@ def estimated_bits(out):
 def estimated_bpp(out, num_pixels):
     """Bits per pixel, num_pixels = N * H * W of the input frames (rate_distortion.py:66, 71-74)."""
     return estimated_bits(out) / float(num_pixels)
+
+
+# ---- reconstruction error (csrc/metrics.hip) ----------------------------------------------------------------------------
+# For frames x (truth) and x_hat (reconstruction), fp32 [C, H, W] in the same units, d = x_hat - x in fp32; per channel c:
+#   mse = mean_(h,w) d^2          rmse = sqrt(mse)          wrmse = sqrt(mean_(h,w) L(h) d^2)
+#   bias = mean d                 mae = mean |d|            max_abs = max |d| (the fp32 value, exact)
+#   nonfinite = count of (h, w) where x or x_hat is NaN / +-inf; a channel with nonfinite > 0 reports NaN in every other
+#   statistic (channels without non-finite values are unaffected).
+# L(h) is the WeatherBench latitude weight: cos(phi_h) / mean_h' cos(phi_h'), phi_h = 90 - 180 h / (H - 1) degrees.
+
+_LAT_CACHE = {}
+
+
+def latitude_weights(H):
+    """WeatherBench latitude weights L(h) of an H-row equiangular grid from 90 N (row 0) to 90 S (row H - 1), float64
+    [H]: mean 1, symmetric, ~0 at the poles.  H >= 2 (the row spacing is 180 / (H - 1) degrees)."""
+    H = int(H)
+    if H < 2:
+        raise ValueError(f"latitude weights need H >= 2 rows from pole to pole (got H = {H})")
+    phi = np.deg2rad(90.0 - 180.0 * np.arange(H, dtype=np.float64) / (H - 1))
+    c = np.cos(phi)
+    return c / c.mean()
+
+
+def _device_weights(lat_weights, H, device):
+    if lat_weights is None:
+        return None
+    if isinstance(lat_weights, str):
+        if lat_weights != "era5":
+            raise ValueError(f"lat_weights must be 'era5', None or an [H] array (got {lat_weights!r})")
+        key = (H, str(device))
+        w = _LAT_CACHE.get(key)
+        if w is None:
+            w = _LAT_CACHE[key] = torch.from_numpy(latitude_weights(H).astype(np.float32)).to(device)
+        return w
+    w = lat_weights.detach().cpu().numpy() if isinstance(lat_weights, torch.Tensor) else np.asarray(lat_weights)
+    if w.shape != (H,):
+        raise ValueError(f"lat_weights must have shape [{H}] (got {tuple(w.shape)})")
+    return torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(device)
+
+
+def reconstruction_error(x_hat, x, lat_weights="era5"):
+    """Per-channel error of the reconstruction `x_hat` against the truth `x`: device fp32 tensors [C, H, W] or
+    [1, C, H, W] of the same shape.  lat_weights: "era5" (latitude_weights(H)), None (L = 1: wrmse = rmse) or an [H]
+    array.  One streaming pass on the GPU (ops.recon_error, the current stream); only C x 6 numbers come back.
+    Returns {"mse", "rmse", "wrmse", "bias", "mae", "max_abs"}: float64 numpy [C], and "nonfinite": int64 numpy [C]."""
+    if not (isinstance(x_hat, torch.Tensor) and isinstance(x, torch.Tensor)):
+        raise TypeError("reconstruction_error: x_hat and x must be torch tensors on the GPU")
+    if tuple(x_hat.shape) != tuple(x.shape):
+        raise ValueError(f"reconstruction_error: x_hat {tuple(x_hat.shape)} and x {tuple(x.shape)} differ in shape")
+    for name, t in (("x_hat", x_hat), ("x", x)):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError(f"reconstruction_error: {name} must be a contiguous fp32 GPU tensor")
+    if x.dim() == 4 and x.shape[0] == 1:
+        x_hat, x = x_hat[0], x[0]
+    if x.dim() != 3:
+        raise ValueError(f"reconstruction_error takes [C, H, W] or [1, C, H, W] frames (got {tuple(x.shape)})")
+    from . import ops
+    C, H, W = x.shape
+    r = ops.recon_error(x_hat, x, _device_weights(lat_weights, H, x.device)).cpu().numpy()
+    f = {k: r[:, i] for i, k in enumerate(ops.RECON_FIELDS)}
+    return dict(mse=f["mse"].copy(), rmse=np.sqrt(f["mse"]), wrmse=np.sqrt(f["wmse"]), bias=f["bias"].copy(),
+                mae=f["mae"].copy(), max_abs=f["max_abs"].copy(), nonfinite=f["nonfinite"].astype(np.int64))

@@ -592,6 +592,35 @@ def probe_sums(x, out, stride=1):
     return out
 
 
+RECON_FIELDS = ("bias", "mse", "wmse", "mae", "max_abs", "nonfinite")   # CRA5_RECON_* order
+
+
+def recon_error(x_hat, x, lat_w=None, out=None):
+    """cra5_recon_error_f32: per-channel error statistics of x_hat against x (both contiguous fp32 device tensors
+    [C, H, W]; lat_w: contiguous fp32 device [H] or None) -> fp64 device tensor [C, len(RECON_FIELDS)] (`out`), in the
+    fields of RECON_FIELDS.  On the current stream; the slab of partials comes from torch's caching allocator."""
+    ts = (x_hat, x) + ((lat_w,) if lat_w is not None else ())
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts):
+        raise TypeError("recon_error takes contiguous fp32 device tensors")
+    if x_hat.dim() != 3 or tuple(x_hat.shape) != tuple(x.shape) or x_hat.device != x.device:
+        raise ValueError(f"recon_error: x_hat {tuple(x_hat.shape)} and x {tuple(x.shape)} must be [C, H, W] of one shape "
+                         "on one device")
+    C, H, W = x.shape
+    if lat_w is not None and (tuple(lat_w.shape) != (H,) or lat_w.device != x.device):
+        raise ValueError(f"recon_error: lat_w must be [{H}] on the frames' device")
+    nb = lib().cra5_recon_error_slab_bytes(C, H, W)
+    if nb == 0:
+        raise ValueError(f"recon_error: unsupported frame shape {(C, H, W)}")
+    slab = torch.empty((nb // 8,), device=x.device, dtype=torch.float64)
+    if out is None:
+        out = torch.empty((C, len(RECON_FIELDS)), device=x.device, dtype=torch.float64)
+    elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (C, len(RECON_FIELDS))):
+        raise TypeError(f"recon_error: out must be a contiguous fp64 device tensor [{C}, {len(RECON_FIELDS)}]")
+    check(lib().cra5_recon_error_f32(_p(x_hat), _p(x), C, H, W, _p(lat_w), _p(slab), nb, _p(out), _stream()),
+          "cra5_recon_error_f32")
+    return out
+
+
 def transpose(x, out=None):
     _dev(x, out)
     R, Cc = x.shape

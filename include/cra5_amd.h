@@ -268,6 +268,26 @@ int cra5_col2im_f32(const float *cols, const float *mean, const float *std, floa
 #define CRA5_PROBE_PARTIALS 256
 int cra5_probe_sums_f32(const float *x, size_t n, size_t stride, float *partials, void *stream);
 
+/* Per-channel reconstruction error of a frame (csrc/metrics.hip): x_hat, x [C][H][W] fp32 (any W; 16-byte aligned
+ * bases take the float4 path), d = x_hat - x.  out [C][CRA5_RECON_FIELDS] fp64, per channel c:
+ *   BIAS = mean d,  MSE = mean d^2,  WMSE = mean lat_w[h] d^2 (lat_w [H] fp32; NULL: weight 1),  MAE = mean |d|,
+ *   MAX_ABS = max |d| (the fp32 value, exact),  NONFINITE = count of (h, w) where x or x_hat is NaN / +-inf;
+ * means are over all H*W positions; a channel with NONFINITE > 0 has NaN in the other five fields.  `slab`: caller-owned
+ * device scratch of >= cra5_recon_error_slab_bytes(C, H, W) bytes (one fp64 record per block, overwritten: no memset).
+ * Two launches on `stream`, fixed reduction order: bit-identical from run to run.  slab_bytes returns 0 for bad
+ * dimensions (C, H, W > 0, H * W < 2^31); the launcher returns CRA5_ERR_ARG for those, for NULL pointers (lat_w may be
+ * NULL) and for a slab that is too small. */
+#define CRA5_RECON_FIELDS 6
+#define CRA5_RECON_BIAS 0
+#define CRA5_RECON_MSE 1
+#define CRA5_RECON_WMSE 2
+#define CRA5_RECON_MAE 3
+#define CRA5_RECON_MAX_ABS 4
+#define CRA5_RECON_NONFINITE 5
+size_t cra5_recon_error_slab_bytes(int C, int H, int W);
+int cra5_recon_error_f32(const float *x_hat, const float *x, int C, int H, int W, const float *lat_w, double *slab,
+                         size_t slab_bytes, double *out, void *stream);
+
 /* out[c][r] = in[r][c] (token-major <-> NCHW plumbing, vit_nlc.py:484, 684). */
 int cra5_transpose_f32(const float *in, int ld_in, float *out, int ld_out, int rows, int cols,
                        void *stream);
