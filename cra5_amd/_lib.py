@@ -132,7 +132,8 @@ class StreamDesyncError(Cra5Error):
     """A rANS stream was decoded to the last symbol, but the coder did not come back to RANS64_L with every word
     consumed: the (tables, indexes) the decoder used are not the encoder's, or the stream is damaged.  The symbols that
     were decoded are NOT the coded ones.  (The reference's decoder has no such check and returns them:
-    rans_interface.cpp:215-284.)"""
+    rans_interface.cpp:215-284.)  The check catches index and table desync and most damage; a flipped bit inside an
+    escape's payload nibbles passes it (bypass bits do not steer the coder) and changes only that one symbol."""
 
 
 def check(rc, what):

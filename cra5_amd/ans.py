@@ -11,26 +11,12 @@ from . import ops
 from ._lib import check, lib
 
 
-def _i32(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
-
-
-def _tables(cdfs, cdfs_sizes, offsets):
-    sizes = _i32(cdfs_sizes).reshape(-1)
-    if isinstance(cdfs, np.ndarray) and cdfs.ndim == 2:
-        c = _i32(cdfs)
-    else:  # list of (possibly ragged) rows, as pybind11 accepts
-        stride = max(len(r) for r in cdfs)
-        c = np.zeros((len(cdfs), stride), dtype=np.int32)
-        for i, r in enumerate(cdfs):
-            c[i, : len(r)] = r
-    return c, sizes, _i32(offsets).reshape(-1)
+_i32, _tables = ops._np_i32, ops._tables
 
 
 class RansEncoder:
     def encode_with_indexes(self, symbols, indexes, cdfs, cdfs_sizes, offsets):
-        c, l, o = _tables(cdfs, cdfs_sizes, offsets)
-        return ops.rans_encode(_i32(symbols), _i32(indexes), c, l, o)
+        return ops.rans_encode(symbols, indexes, cdfs, cdfs_sizes, offsets)
 
 
 class BufferedRansEncoder:
@@ -53,12 +39,7 @@ class BufferedRansEncoder:
                                            c.shape[1], l.ctypes.data, o.ctypes.data), "cra5_rans_encoder_push")
 
     def flush(self):
-        out, n = ctypes.c_void_p(), ctypes.c_size_t()
-        check(lib().cra5_rans_encoder_flush(self._h, ctypes.byref(out), ctypes.byref(n)), "cra5_rans_encoder_flush")
-        try:
-            return ctypes.string_at(out.value, n.value)
-        finally:
-            lib().cra5_free(out)
+        return ops._encoded("cra5_rans_encoder_flush", self._h)
 
 
 class RansDecoder:
@@ -73,8 +54,7 @@ class RansDecoder:
             self._h = None
 
     def decode_with_indexes(self, encoded, indexes, cdfs, cdfs_sizes, offsets):
-        c, l, o = _tables(cdfs, cdfs_sizes, offsets)
-        return ops.rans_decode(encoded, _i32(indexes), c, l, o).tolist()
+        return ops.rans_decode(encoded, indexes, cdfs, cdfs_sizes, offsets).tolist()
 
     def set_stream(self, encoded):
         buf = (ctypes.c_char * len(encoded)).from_buffer_copy(encoded)

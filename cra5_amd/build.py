@@ -26,7 +26,7 @@ LIB = os.path.join(HERE, "libcra5_amd.so")
 SOURCES = ["host_entropy.cpp", "gemm_f32.hip", "gemm_split_f16.hip", "attention_f32.hip", "attention_split_f16.hip",
            "elementwise.hip", "hyper.hip", "metrics.hip", "runtime.hip"]
 SOURCES = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
-HEADERS = [os.path.join(ROOT, "include", "cra5_amd.h"), os.path.join(CSRC, "split.h"),
+HEADERS = [os.path.join(ROOT, "include", "cra5_amd.h"), os.path.join(CSRC, "split.h"), os.path.join(CSRC, "rans_resolve.h"),
            os.path.join(CSRC, "gemm_split_epilogue.inc"), os.path.join(CSRC, "gemm_split_epilogue_fast.inc"),
            os.path.join(CSRC, "gemm_split_epilogue_unembed.inc")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

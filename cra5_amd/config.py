@@ -8,8 +8,8 @@ package that turns `CRA5_*` variables into settings ("model
 Not settings, and therefore not here:
   * the ARCHITECTURE (`cra5_amd.vaeformer.config_for`: the reference's ddconfig / priorconfig dictionaries);
   * what the launcher owns (RANK / WORLD_SIZE / MASTER_*, HIP_VISIBLE_DEVICES);
-  * bit-identical implementation alternatives kept for tests (`VAEformer.compact_records`, `.fused_unembed`,
-    `.resolve_on_gpu`, `.attn_balanced`, `.f16_layout`): plain attributes a test flips, no environment variable;
+  * bit-identical implementation alternatives that guard fallbacks (`VAEformer.fused_unembed`, `.attn_balanced`,
+    `.f16_layout`): plain attributes a test flips, no environment variable;
   * test hooks (CRA5_TEST_*, CRA5_SHARE_GPU, CRA5_FORCE_DIST, CRA5_DIST_BACKEND) and CRA5_LIB (which library file to
     load: a build matter, cra5_amd/_lib.py).
 The native library reads NO environment variable (only the -DCRA5_GEMM_TRACE variant build that tools/gemm_trace.py

@@ -8,6 +8,9 @@
 
 #include "../../include/cra5_amd.h"
 #include "split.h"
+#pragma clang force_cuda_host_device begin
+#include "rans_resolve.h"
+#pragma clang force_cuda_host_device end
 
 CRA5_RANGE_TU(elementwise)
 #ifdef CRA5_RANGE_CHECK
@@ -476,6 +479,13 @@ __global__ __launch_bounds__(256) void unary_kernel(const float *__restrict__ x,
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ float phi(float u) { return 0.5f * erfcf(-0.70710678118654752440f * u); }
 
+// bounded scale -> CDF row: n_table - 1, minus one for every entry but the last that the scale does not exceed (tb: LDS)
+__device__ __forceinline__ int scale_index(const float *tb, int n_table, float s) {
+  int id = n_table - 1;
+  for (int t = 0; t < n_table - 1; ++t) id -= (s <= tb[t]) ? 1 : 0;
+  return id;
+}
+
 __global__ __launch_bounds__(256) void gaussian_conditional_kernel(
     const float *__restrict__ y, const int32_t *__restrict__ sym_in, const float *__restrict__ scales,
     const float *__restrict__ means, const float *__restrict__ table, int n_table, float scale_bound,
@@ -490,11 +500,7 @@ __global__ __launch_bounds__(256) void gaussian_conditional_kernel(
     float q;                                        // quantised residual
     if (y) q = rintf(y[e] - mu);                    // torch.round = half-to-even
     else q = (float)sym_in[e];
-    if (idx) {
-      int id = n_table - 1;
-      for (int t = 0; t < n_table - 1; ++t) id -= (s <= tb[t]) ? 1 : 0;
-      idx[e] = id;
-    }
+    if (idx) idx[e] = scale_index(tb, n_table, s);
     if (sym) sym[e] = (int32_t)q;
     const float yh = q + mu;
     if (y_hat) y_hat[e] = yh;
@@ -517,101 +523,72 @@ __global__ __launch_bounds__(256) void gaussian_conditional_compact_kernel(
   for (int i = threadIdx.x; i < n_table; i += blockDim.x) tb[i] = table[i];
   __syncthreads();
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-    if (idx8) {
-      const float s = fmaxf(scales[e], scale_bound);  // LowerBound
-      int id = n_table - 1;
-      for (int t = 0; t < n_table - 1; ++t) id -= (s <= tb[t]) ? 1 : 0;
-      idx8[e] = (uint8_t)id;
-    }
+    if (idx8) idx8[e] = (uint8_t)scale_index(tb, n_table, fmaxf(scales[e], scale_bound));  // (LowerBound)
     if (y_hat) y_hat[e] = (float)sym16_in[e] + means[e];
   }
 }
 
 // ---------------------------------------------------------------------------------------
 // Symbol -> (start, range, escape payload) against the quantised CDF tables, on the device
-// (rans_interface.cpp:121-150; the host encoder then only updates its state).
+// (rans_resolve.h, the host coder's own resolve step; the host encoder then only updates its state).
+// Rec stores the escape part of each record and says whether the compact launcher must report an overflow.
 // ---------------------------------------------------------------------------------------
+// 32-bit records: raw payload + esc = 1 + payload nibbles (0: regular symbol, 255: invalid index)
+struct WideRecords {
+  uint32_t *__restrict__ raw;
+  uint8_t *__restrict__ esc;
+  __device__ bool invalid(size_t e) const {
+    raw[e] = 0u;
+    esc[e] = 255;
+    return false;
+  }
+  __device__ bool store(size_t e, const cra5_rans::Resolved &r) const {
+    raw[e] = r.raw;
+    esc[e] = r.escape ? (uint8_t)(r.n_nibbles + 1) : (uint8_t)0;
+    return false;
+  }
+  __device__ void finish(bool) const {}
+};
+
+// COMPACT records: rec16 = 0 for a regular symbol, (1 + payload nibbles) << 12 | payload for an escape whose payload
+// fits 12 bits (|symbol| up to ~2000 beyond its table row), 0xFFFF + *overflow = 1 otherwise (the caller then takes the
+// 32-bit records): 6 instead of 9 bytes per latent over PCIe.
+struct CompactRecords {
+  uint16_t *__restrict__ rec16;
+  int32_t *__restrict__ overflow;
+  __device__ bool invalid(size_t e) const {
+    rec16[e] = 0xFFFFu;
+    return true;
+  }
+  __device__ bool store(size_t e, const cra5_rans::Resolved &r) const {
+    const bool wide = r.escape && r.raw >= 4096u;
+    rec16[e] = !r.escape ? (uint16_t)0 : wide ? (uint16_t)0xFFFFu : (uint16_t)(((uint32_t)(r.n_nibbles + 1) << 12) | r.raw);
+    return wide;
+  }
+  __device__ void finish(bool bad) const {
+    if (bad) atomicOr(overflow, 1);
+  }
+};
+
+template <class Rec>
 __global__ __launch_bounds__(256) void resolve_symbols_kernel(
     const int32_t *__restrict__ sym, const int32_t *__restrict__ idx, size_t n, const int32_t *__restrict__ cdfs,
     int n_cdfs, int stride, const int32_t *__restrict__ sizes, const int32_t *__restrict__ offsets,
-    uint32_t *__restrict__ sr, uint32_t *__restrict__ raw, uint8_t *__restrict__ esc) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-    const int ci = idx[e];
-    if (ci < 0 || ci >= n_cdfs || sizes[ci] < 2 || sizes[ci] > stride) {
-      sr[e] = 0u;
-      raw[e] = 0u;
-      esc[e] = 255;
-      continue;
-    }
-    const int32_t *cdf = cdfs + (size_t)ci * stride;
-    const int max_value = sizes[ci] - 2;
-    int value = sym[e] - offsets[ci];
-    uint32_t r = 0u;
-    if (value < 0) {
-      r = (uint32_t)(-2 * value - 1);
-      value = max_value;
-    } else if (value >= max_value) {
-      r = (uint32_t)(2 * (value - max_value));
-      value = max_value;
-    }
-    const uint32_t start = (uint32_t)cdf[value] & 0xFFFFu;
-    const uint32_t range = (uint32_t)(cdf[value + 1] - cdf[value]) & 0xFFFFu;
-    sr[e] = start | (range << 16);
-    raw[e] = r;
-    uint8_t ec = 0;
-    if (value == max_value) {
-      int nn = 0;
-      while (nn < 8 && (r >> (4 * nn)) != 0u) ++nn;
-      ec = (uint8_t)(nn + 1);
-    }
-    esc[e] = ec;
-  }
-}
-
-// The same resolve step writing COMPACT records: rec16 = 0 for a regular symbol, (1 + payload nibbles) << 12 | payload
-// for an escape whose payload fits 12 bits (|symbol| up to ~2000 beyond its table row), 0xFFFF + *overflow = 1 otherwise
-// (the caller then takes the 32-bit records of resolve_symbols_kernel): 6 instead of 9 bytes per latent over PCIe.
-__global__ __launch_bounds__(256) void resolve_symbols_compact_kernel(
-    const int32_t *__restrict__ sym, const int32_t *__restrict__ idx, size_t n, const int32_t *__restrict__ cdfs,
-    int n_cdfs, int stride, const int32_t *__restrict__ sizes, const int32_t *__restrict__ offsets,
-    uint32_t *__restrict__ sr, uint16_t *__restrict__ rec16, int32_t *__restrict__ overflow) {
+    uint32_t *__restrict__ sr, Rec rec) {
+  const cra5_rans::Tables t{cdfs, n_cdfs, stride, sizes, offsets};
   bool bad = false;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
     const int ci = idx[e];
-    if (ci < 0 || ci >= n_cdfs || sizes[ci] < 2 || sizes[ci] > stride) {
+    if (!cra5_rans::row_ok(t, ci)) {
       sr[e] = 0u;
-      rec16[e] = 0xFFFFu;
-      bad = true;
+      bad |= rec.invalid(e);
       continue;
     }
-    const int32_t *cdf = cdfs + (size_t)ci * stride;
-    const int max_value = sizes[ci] - 2;
-    int value = sym[e] - offsets[ci];
-    uint32_t r = 0u;
-    if (value < 0) {
-      r = (uint32_t)(-2 * value - 1);
-      value = max_value;
-    } else if (value >= max_value) {
-      r = (uint32_t)(2 * (value - max_value));
-      value = max_value;
-    }
-    const uint32_t start = (uint32_t)cdf[value] & 0xFFFFu;
-    const uint32_t range = (uint32_t)(cdf[value + 1] - cdf[value]) & 0xFFFFu;
-    sr[e] = start | (range << 16);
-    uint16_t rec = 0;
-    if (value == max_value) {
-      if (r >= 4096u) {
-        rec = 0xFFFFu;
-        bad = true;
-      } else {
-        int nn = 0;
-        while (nn < 3 && (r >> (4 * nn)) != 0u) ++nn;
-        rec = (uint16_t)(((uint32_t)(nn + 1) << 12) | r);
-      }
-    }
-    rec16[e] = rec;
+    const cra5_rans::Resolved r = cra5_rans::resolve(t, sym[e], ci);
+    sr[e] = r.start | (r.range << 16);
+    bad |= rec.store(e, r);
   }
-  if (bad) atomicOr(overflow, 1);
+  rec.finish(bad);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -855,8 +832,8 @@ int cra5_rans_resolve_symbols_i32(const int32_t *symbols, const int32_t *indexes
                                   uint32_t *start_range, uint32_t *raw, uint8_t *esc, void *stream) {
   if (!symbols || !indexes || !cdfs || !cdf_sizes || !offsets || !start_range || !raw || !esc) return CRA5_ERR_ARG;
   if (n == 0 || n_cdfs <= 0 || cdf_stride < 2) return CRA5_ERR_ARG;
-  hipLaunchKernelGGL(resolve_symbols_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, symbols, indexes, n,
-                     cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets, start_range, raw, esc);
+  hipLaunchKernelGGL(resolve_symbols_kernel<WideRecords>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, symbols,
+                     indexes, n, cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets, start_range, WideRecords{raw, esc});
   return (int)hipGetLastError();
 }
 
@@ -867,8 +844,9 @@ int cra5_rans_resolve_symbols_compact(const int32_t *symbols, const int32_t *ind
   if (n == 0 || n_cdfs <= 0 || cdf_stride < 2) return CRA5_ERR_ARG;
   int rc = (int)hipMemsetAsync(overflow, 0, sizeof(int32_t), (hipStream_t)stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(resolve_symbols_compact_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, symbols,
-                     indexes, n, cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets, start_range, rec16, overflow);
+  hipLaunchKernelGGL(resolve_symbols_kernel<CompactRecords>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
+                     symbols, indexes, n, cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets, start_range,
+                     CompactRecords{rec16, overflow});
   return (int)hipGetLastError();
 }
 

@@ -8,12 +8,14 @@
 // Design differences from the reference (same bytes out):
 //   * flat int32 arrays in, no Python-list marshalling, no GIL, no global state;
 //   * the encoder never materialises the (start, range, bypass) symbol vector: one
-//     counting pass sizes the word buffer, then one backward pass codes straight from
-//     the symbol array (bypass nibbles are regenerated in reverse order);
+//     backward pass codes straight from the symbol array (bypass nibbles are regenerated
+//     in reverse order), resolving each symbol with rans_resolve.h - the step the device
+//     resolver shares;
 //   * the decoder finds the bin with a binary search instead of the reference's linear
 //     `find_if` scan (identical result on a strictly increasing CDF row);
 //   * range-checked: bad table indexes / truncated streams return an error code.
 #include "../../include/cra5_amd.h"
+#include "rans_resolve.h"
 
 #include <algorithm>
 #include <atomic>
@@ -26,53 +28,9 @@
 
 namespace {
 
-constexpr uint64_t kRansL = 1ull << 31;  // rans64.h RANS64_L
-constexpr uint32_t kProbBits = 16;       // rans_interface.cpp:49
-constexpr uint32_t kBypassBits = 4;      // rans_interface.cpp:51
-constexpr uint32_t kBypassMax = (1u << kBypassBits) - 1;
+using namespace cra5_rans;
 
-struct Tables {
-  const int32_t *cdfs;
-  int n_cdfs;
-  int stride;
-  const int32_t *sizes;
-  const int32_t *offsets;
-};
-
-// One coded symbol resolved against its table: bin + escape payload.
-struct Resolved {
-  uint32_t start, range;
-  bool escape;
-  uint32_t raw;
-  int n_nibbles;
-};
-
-inline int nibbles_of(uint32_t raw) {
-  int n = 0;
-  while (n < 8 && (raw >> (n * kBypassBits)) != 0) ++n;
-  return n;
-}
-
-inline Resolved resolve(const Tables &t, int32_t sym, int32_t ci) {
-  const int32_t *cdf = t.cdfs + static_cast<size_t>(ci) * t.stride;
-  const int32_t max_value = t.sizes[ci] - 2;
-  int32_t value = sym - t.offsets[ci];
-  Resolved r{0, 0, false, 0, 0};
-  if (value < 0) {
-    r.raw = static_cast<uint32_t>(-2 * value - 1);
-    value = max_value;
-  } else if (value >= max_value) {
-    r.raw = static_cast<uint32_t>(2 * (value - max_value));
-    value = max_value;
-  }
-  r.start = static_cast<uint32_t>(cdf[value]) & 0xFFFFu;
-  r.range = static_cast<uint32_t>(cdf[value + 1] - cdf[value]) & 0xFFFFu;
-  if (value == max_value) {
-    r.escape = true;
-    r.n_nibbles = nibbles_of(r.raw);
-  }
-  return r;
-}
+bool tables_ok(const Tables &t) { return t.cdfs && t.sizes && t.offsets && t.n_cdfs > 0 && t.stride >= 2; }
 
 // Division by a bin's frequency as a multiplication (round 6).  Rans64EncPut computes x / freq and x % freq with a 64-bit
 // divide on the coder's serial dependency chain (~20 cycles of the ~28 a symbol takes); the published rans64 encoder
@@ -158,65 +116,65 @@ struct Encoder {
   }
 };
 
+// The stream writer of every encoder: `code(e)` pushes the symbols, last first, into an encoder that writes backward
+// from the end of a `cap`-word buffer (one word more than the stream can take: put() stores below the cursor before it
+// knows whether it keeps the word); the flushed stream leaves as one malloc'ed copy.  -> code()'s status, or ALLOC.
+template <class Code>
+int write_stream(size_t cap, Code &&code, uint8_t **out, size_t *out_len) {
+  uint32_t *buf = static_cast<uint32_t *>(std::malloc(cap * sizeof(uint32_t)));
+  if (!buf) return CRA5_ERR_ALLOC;
+  Encoder e;
+  e.ptr = buf + cap;
+  int rc = code(e);
+  if (rc == CRA5_OK) {
+    e.ptr -= 2;  // Rans64EncFlush
+    e.ptr[0] = static_cast<uint32_t>(e.x);
+    e.ptr[1] = static_cast<uint32_t>(e.x >> 32);
+    const size_t nbytes = static_cast<size_t>((buf + cap) - e.ptr) * sizeof(uint32_t);
+    uint8_t *res = static_cast<uint8_t *>(std::malloc(nbytes));
+    if (res) {
+      std::memcpy(res, e.ptr, nbytes);
+      *out = res;
+      *out_len = nbytes;
+    } else {
+      rc = CRA5_ERR_ALLOC;
+    }
+  }
+  std::free(buf);
+  return rc;
+}
+
 int encode_impl(const int32_t *symbols, const int32_t *indexes, size_t n, const Tables &t,
                 uint8_t **out, size_t *out_len) {
   if (!out || !out_len || (n && (!symbols || !indexes))) return CRA5_ERR_ARG;
-  // One pass, last symbol first.  Every coded sub-symbol emits at most one 32-bit word and a symbol
-  // has at most 1 bin + 1 count nibble + 8 payload nibbles (a uint32 payload), so 10 n + 2 words always
-  // suffice; the words are written from the END of the buffer, only the pages actually reached are
-  // ever touched (a frame: 106 MB reserved, ~4 MB used).  If that reservation fails, count first.
-  size_t cap = 10 * n + 3;   // (+ 1: put() writes the word below the cursor before it knows whether it keeps it)
-  uint32_t *buf = static_cast<uint32_t *>(std::malloc(cap * sizeof(uint32_t)));
-  if (!buf) {
-    size_t n_sub = 0;
-    for (size_t i = 0; i < n; ++i) {
+  // One pass, last symbol first; inside a symbol the reference pushes [bin, count nibble, payload nibbles lsb-first]
+  // and pops in reverse.
+  auto code = [&](Encoder &e) -> int {
+    for (size_t i = n; i-- > 0;) {
       const int32_t ci = indexes[i];
-      if (ci < 0 || ci >= t.n_cdfs || t.sizes[ci] < 2 || t.sizes[ci] > t.stride) return CRA5_ERR_INDEX;
+      if (!row_ok(t, ci)) return CRA5_ERR_INDEX;
       const Resolved r = resolve(t, symbols[i], ci);
-      n_sub += 1;
-      if (r.escape) n_sub += static_cast<size_t>(r.n_nibbles) / kBypassMax + 1 + r.n_nibbles;
+      if (r.range == 0) return CRA5_ERR_INDEX;   // malformed table (zero-width bin): would divide by zero in put()
+      if (r.escape) {
+        for (int j = r.n_nibbles - 1; j >= 0; --j) e.put_bits((r.raw >> (j * kBypassBits)) & kBypassMax);
+        e.put_bits(static_cast<uint32_t>(r.n_nibbles));
+      }
+      e.put(r.start, r.range);
     }
-    cap = n_sub + 3;
-    buf = static_cast<uint32_t *>(std::malloc(cap * sizeof(uint32_t)));
-    if (!buf) return CRA5_ERR_ALLOC;
+    return CRA5_OK;
+  };
+  // Every coded sub-symbol emits at most one 32-bit word and a symbol has at most 1 bin + 1 count nibble + 8 payload
+  // nibbles, so 10 n + 2 words always suffice; the words are written from the END of the buffer, only the pages
+  // actually reached are ever touched (a frame: 106 MB reserved, ~4 MB used).  If that reservation fails, count first.
+  const int rc = write_stream(10 * n + 3, code, out, out_len);
+  if (rc != CRA5_ERR_ALLOC) return rc;
+  size_t words = 3;
+  for (size_t i = 0; i < n; ++i) {
+    if (!row_ok(t, indexes[i])) return CRA5_ERR_INDEX;
+    const Resolved r = resolve(t, symbols[i], indexes[i]);
+    words += r.escape ? 2 + static_cast<size_t>(r.n_nibbles) : 1;
   }
-  Encoder e;
-  e.ptr = buf + cap;
-  // inside a symbol the reference pushes [bin, count nibbles (15,15,..,rem), payload nibbles
-  // lsb-first] and pops in reverse.
-  for (size_t i = n; i-- > 0;) {
-    const int32_t ci = indexes[i];
-    if (ci < 0 || ci >= t.n_cdfs || t.sizes[ci] < 2 || t.sizes[ci] > t.stride) {
-      std::free(buf);
-      return CRA5_ERR_INDEX;
-    }
-    const Resolved r = resolve(t, symbols[i], ci);
-    if (r.range == 0) {   // malformed table (zero-width bin): would divide by zero in put()
-      std::free(buf);
-      return CRA5_ERR_INDEX;
-    }
-    if (r.escape) {
-      for (int j = r.n_nibbles - 1; j >= 0; --j) e.put_bits((r.raw >> (j * kBypassBits)) & kBypassMax);
-      const uint32_t full = static_cast<uint32_t>(r.n_nibbles) / kBypassMax;
-      e.put_bits(static_cast<uint32_t>(r.n_nibbles) - full * kBypassMax);
-      for (uint32_t k = 0; k < full; ++k) e.put_bits(kBypassMax);
-    }
-    e.put(r.start, r.range);
-  }
-  e.ptr -= 2;  // Rans64EncFlush
-  e.ptr[0] = static_cast<uint32_t>(e.x);
-  e.ptr[1] = static_cast<uint32_t>(e.x >> 32);
-  const size_t nbytes = static_cast<size_t>((buf + cap) - e.ptr) * sizeof(uint32_t);
-  uint8_t *res = static_cast<uint8_t *>(std::malloc(nbytes));
-  if (!res) {
-    std::free(buf);
-    return CRA5_ERR_ALLOC;
-  }
-  std::memcpy(res, e.ptr, nbytes);
-  std::free(buf);
-  *out = res;
-  *out_len = nbytes;
-  return CRA5_OK;
+  return write_stream(words, code, out, out_len);
 }
 
 struct Decoder {
@@ -238,6 +196,17 @@ struct Decoder {
     x >>= kBypassBits;
     if (x < kRansL) x = (x << 32) | word();
     return val;
+  }
+  // renormalisation by select: the word below the cursor is read either way (from the last word of the stream when
+  // the cursor is at its end) and taken when the state fell below 2^31 - ~40 % of the symbols, a coin flip as a branch
+  inline void renorm() {
+    const bool need = x < kRansL;
+    const bool room = p + 4 <= end;
+    uint32_t w;
+    std::memcpy(&w, room ? p : end - 4, 4);
+    ok = ok && (room || !need);
+    x = need ? ((x << 32) | w) : x;
+    p += need ? 4 : 0;
   }
 };
 
@@ -300,7 +269,7 @@ int decode_symbols(Decoder &d, const IdxT *indexes, size_t n, const Tables &t, O
     if (ci < 0 || ci >= t.n_cdfs) return CRA5_ERR_INDEX;
     RowDec &r = rows[static_cast<size_t>(ci)];
     if (!r.built) {
-      if (t.sizes[ci] < 2 || t.sizes[ci] > t.stride) return CRA5_ERR_INDEX;
+      if (!row_ok(t, ci)) return CRA5_ERR_INDEX;
       build_row_dec(r, store[static_cast<size_t>(ci)], t.cdfs + static_cast<size_t>(ci) * t.stride, t.sizes[ci], t.offsets[ci]);
     }
     const int32_t cum = static_cast<int32_t>(d.x & mask);
@@ -327,17 +296,7 @@ int decode_symbols(Decoder &d, const IdxT *indexes, size_t n, const Tables &t, O
       freq = static_cast<uint32_t>(cdf[s + 1] - cdf[s]);
     }
     d.x = freq * (d.x >> kProbBits) + static_cast<uint64_t>(cum) - start;
-    {
-      // renormalisation by select: the word below the cursor is read either way (from the last word of the stream when
-      // the cursor is at its end) and taken when the state fell below 2^31 - ~40 % of the symbols, a coin flip as a branch
-      const bool need = d.x < kRansL;
-      const bool room = d.p + 4 <= d.end;
-      uint32_t w;
-      std::memcpy(&w, room ? d.p : d.end - 4, 4);
-      d.ok = d.ok && (room || !need);
-      d.x = need ? ((d.x << 32) | w) : d.x;
-      d.p += need ? 4 : 0;
-    }
+    d.renorm();
     int32_t value = s;
     if (value == r.max_value) {
       // An escape = count nibble + n payload nibbles, each of which get_bits() follows with a renormalisation when the
@@ -355,15 +314,7 @@ int decode_symbols(Decoder &d, const IdxT *indexes, size_t n, const Tables &t, O
         const int r2 = T - t1;
         uint64_t v = d.x & ((1ull << (4 * t1)) - 1);
         d.x >>= 4 * t1;
-        {
-          const bool need = d.x < kRansL;
-          const bool room = d.p + 4 <= d.end;
-          uint32_t w;
-          std::memcpy(&w, room ? d.p : d.end - 4, 4);
-          d.ok = d.ok && (room || !need);
-          d.x = need ? ((d.x << 32) | w) : d.x;
-          d.p += need ? 4 : 0;
-        }
+        d.renorm();
         v |= (d.x & ((1ull << (4 * r2)) - 1)) << (4 * t1);
         d.x >>= 4 * r2;
         raw = static_cast<uint32_t>(v >> kBypassBits);
@@ -410,11 +361,12 @@ int decode_impl(const uint8_t *enc, size_t len, const IdxT *indexes, size_t n, c
   if (rc) return rc;
   const int rs = decode_symbols(d, indexes, n, t, out);
   if (rs) return rs;
-  // End-state check (the reference has none: rans_interface.cpp:215-284 hands back whatever it decoded).  rANS is a
-  // bijection: the encoder started from RANS64_L (Rans64EncInit) and wrote exactly the words the decoder needs, so
-  // after the last symbol of a stream decoded with the ENCODER's tables and indexes the state is RANS64_L again and
-  // no word is left.  Anything else means the symbols handed back are not the ones that were coded: a CDF index that
-  // differs from the encoder's (h_s evaluated on another platform), the wrong tables, or a damaged stream.
+  // End-state check (the reference has none: rans_interface.cpp:215-284 hands back whatever it decoded).  The encoder
+  // started from RANS64_L (Rans64EncInit) and wrote exactly the words the decoder needs, so a stream decoded with the
+  // ENCODER's tables and indexes ends at RANS64_L with no word left.  A CDF index that differs from the encoder's (h_s
+  // evaluated on another platform), the wrong tables and most damage to the stream end anywhere else.  A flipped bit
+  // inside an escape's payload nibbles does not: bypass bits pass through the state without steering the coder, so
+  // that stream still ends at RANS64_L and only the one symbol's value is wrong.
   if (d.x != kRansL || d.p != d.end) return CRA5_ERR_DESYNC;
   return CRA5_OK;
 }
@@ -460,114 +412,71 @@ int cra5_rans_encode_with_indexes(const int32_t *symbols, const int32_t *indexes
                                   const int32_t *cdfs, int n_cdfs, int cdf_stride,
                                   const int32_t *cdf_sizes, const int32_t *offsets, uint8_t **out,
                                   size_t *out_len) {
-  if (!cdfs || !cdf_sizes || !offsets || n_cdfs <= 0 || cdf_stride < 2) return CRA5_ERR_ARG;
-  return encode_impl(symbols, indexes, n, Tables{cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets}, out, out_len);
+  const Tables t{cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets};
+  if (!tables_ok(t)) return CRA5_ERR_ARG;
+  return encode_impl(symbols, indexes, n, t, out, out_len);
 }
 
 int cra5_rans_encode_resolved_compact(const uint32_t *start_range, const uint16_t *rec16, size_t n, uint8_t **out,
                                       size_t *out_len) {
   if (!out || !out_len || (n && (!start_range || !rec16))) return CRA5_ERR_ARG;
-  const size_t cap = 10 * n + 3;   // see encode_impl
-  uint32_t *buf = static_cast<uint32_t *>(std::malloc(cap * sizeof(uint32_t)));
-  if (!buf) return CRA5_ERR_ALLOC;
-  Encoder e;
-  e.ptr = buf + cap;
-  for (size_t i = n; i-- > 0;) {
-    const uint32_t sr = start_range[i];
-    const uint32_t rec = rec16[i];
-    if (rec) {
-      if (rec == 0xFFFFu) {   // payload beyond 12 bits / invalid index: the caller uses the 32-bit records
-        std::free(buf);
-        return CRA5_ERR_RANGE;
+  return write_stream(10 * n + 3, [&](Encoder &e) -> int {   // (capacity: see encode_impl)
+    for (size_t i = n; i-- > 0;) {
+      const uint32_t sr = start_range[i];
+      const uint32_t rec = rec16[i];
+      if (rec) {
+        if (rec == 0xFFFFu) return CRA5_ERR_RANGE;   // payload beyond 12 bits / invalid index: the caller uses the 32-bit records
+        const int n_nibbles = static_cast<int>(rec >> 12) - 1;
+        const uint32_t r = rec & 0xFFFu;
+        // 0-3 payload nibbles and no payload bit above them (put_nibbles would OR it into the coder state)
+        if (n_nibbles < 0 || n_nibbles > 3 || (r >> (4 * n_nibbles)) != 0) return CRA5_ERR_INDEX;
+        // payload nibbles most significant first, then the count nibble: one shifted word (<= 4 nibbles)
+        e.put_nibbles((r << kBypassBits) | static_cast<uint32_t>(n_nibbles), n_nibbles + 1);
       }
-      const int n_nibbles = static_cast<int>(rec >> 12) - 1;
-      const uint32_t r = rec & 0xFFFu;
-      if (n_nibbles < 0 || n_nibbles > 3) {
-        std::free(buf);
-        return CRA5_ERR_INDEX;
-      }
-      // payload nibbles most significant first, then the count nibble: one shifted word (<= 4 nibbles)
-      e.put_nibbles((r << kBypassBits) | static_cast<uint32_t>(n_nibbles), n_nibbles + 1);
+      const uint32_t freq = sr >> 16;
+      if (!freq) return CRA5_ERR_INDEX;   // a zero-width bin cannot be coded (malformed table)
+      e.put(sr & 0xFFFFu, freq);
     }
-    const uint32_t freq = sr >> 16;
-    if (!freq) {
-      std::free(buf);
-      return CRA5_ERR_INDEX;
-    }
-    e.put(sr & 0xFFFFu, freq);
-  }
-  e.ptr -= 2;  // Rans64EncFlush
-  e.ptr[0] = static_cast<uint32_t>(e.x);
-  e.ptr[1] = static_cast<uint32_t>(e.x >> 32);
-  const size_t nbytes = static_cast<size_t>((buf + cap) - e.ptr) * sizeof(uint32_t);
-  uint8_t *res = static_cast<uint8_t *>(std::malloc(nbytes));
-  if (!res) {
-    std::free(buf);
-    return CRA5_ERR_ALLOC;
-  }
-  std::memcpy(res, e.ptr, nbytes);
-  std::free(buf);
-  *out = res;
-  *out_len = nbytes;
-  return CRA5_OK;
+    return CRA5_OK;
+  }, out, out_len);
 }
 
 int cra5_rans_encode_resolved(const uint32_t *start_range, const uint32_t *raw, const uint8_t *esc, size_t n,
                               uint8_t **out, size_t *out_len) {
   if (!out || !out_len || (n && (!start_range || !raw || !esc))) return CRA5_ERR_ARG;
-  const size_t cap = 10 * n + 3;   // see encode_impl
-  uint32_t *buf = static_cast<uint32_t *>(std::malloc(cap * sizeof(uint32_t)));
-  if (!buf) return CRA5_ERR_ALLOC;
-  Encoder e;
-  e.ptr = buf + cap;
-  for (size_t i = n; i-- > 0;) {
-    const uint32_t sr = start_range[i];
-    const uint32_t ec = esc[i];
-    if (ec) {
-      if (ec > 9) {
-        std::free(buf);
-        return CRA5_ERR_INDEX;
+  return write_stream(10 * n + 3, [&](Encoder &e) -> int {   // (capacity: see encode_impl)
+    for (size_t i = n; i-- > 0;) {
+      const uint32_t sr = start_range[i];
+      const uint32_t ec = esc[i];
+      if (ec) {
+        if (ec > 9) return CRA5_ERR_INDEX;
+        const int n_nibbles = static_cast<int>(ec) - 1;
+        const uint32_t r = raw[i];
+        for (int j = n_nibbles - 1; j >= 0; --j) e.put_bits((r >> (j * kBypassBits)) & kBypassMax);
+        e.put_bits(static_cast<uint32_t>(n_nibbles));
       }
-      const int n_nibbles = static_cast<int>(ec) - 1;
-      const uint32_t r = raw[i];
-      for (int j = n_nibbles - 1; j >= 0; --j) e.put_bits((r >> (j * kBypassBits)) & kBypassMax);
-      e.put_bits(static_cast<uint32_t>(n_nibbles));   // n_nibbles <= 8 < 15: one count nibble
+      const uint32_t freq = sr >> 16;
+      if (!freq) return CRA5_ERR_INDEX;   // a zero-width bin cannot be coded (malformed table)
+      e.put(sr & 0xFFFFu, freq);
     }
-    const uint32_t freq = sr >> 16;
-    if (!freq) {   // a zero-width bin cannot be coded (malformed table)
-      std::free(buf);
-      return CRA5_ERR_INDEX;
-    }
-    e.put(sr & 0xFFFFu, freq);
-  }
-  e.ptr -= 2;  // Rans64EncFlush
-  e.ptr[0] = static_cast<uint32_t>(e.x);
-  e.ptr[1] = static_cast<uint32_t>(e.x >> 32);
-  const size_t nbytes = static_cast<size_t>((buf + cap) - e.ptr) * sizeof(uint32_t);
-  uint8_t *res = static_cast<uint8_t *>(std::malloc(nbytes));
-  if (!res) {
-    std::free(buf);
-    return CRA5_ERR_ALLOC;
-  }
-  std::memcpy(res, e.ptr, nbytes);
-  std::free(buf);
-  *out = res;
-  *out_len = nbytes;
-  return CRA5_OK;
+    return CRA5_OK;
+  }, out, out_len);
 }
 
 int cra5_rans_decode_with_indexes(const uint8_t *encoded, size_t len, const int32_t *indexes, size_t n,
                                   const int32_t *cdfs, int n_cdfs, int cdf_stride,
                                   const int32_t *cdf_sizes, const int32_t *offsets, int32_t *out) {
-  if (!cdfs || !cdf_sizes || !offsets || n_cdfs <= 0 || cdf_stride < 2) return CRA5_ERR_ARG;
-  return decode_impl(encoded, len, indexes, n, Tables{cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets}, out);
+  const Tables t{cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets};
+  if (!tables_ok(t)) return CRA5_ERR_ARG;
+  return decode_impl(encoded, len, indexes, n, t, out);
 }
 
 int cra5_rans_decode_with_indexes_u8_i16(const uint8_t *encoded, size_t len, const uint8_t *indexes, size_t n,
                                          const int32_t *cdfs, int n_cdfs, int cdf_stride, const int32_t *cdf_sizes,
                                          const int32_t *offsets, int16_t *out) {
-  if (!cdfs || !cdf_sizes || !offsets || n_cdfs <= 0 || cdf_stride < 2) return CRA5_ERR_ARG;
-  return decode_impl(encoded, len, indexes, n, Tables{cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets}, out);
+  const Tables t{cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets};
+  if (!tables_ok(t)) return CRA5_ERR_ARG;
+  return decode_impl(encoded, len, indexes, n, t, out);
 }
 
 int cra5_rans_encode_batch(int n_streams, const int32_t *const *symbols, const int32_t *const *indexes,
@@ -609,25 +518,19 @@ void cra5_rans_encoder_free(void *enc) { delete static_cast<BufferedEncoder *>(e
 int cra5_rans_encoder_push(void *enc, const int32_t *symbols, const int32_t *indexes, size_t n,
                            const int32_t *cdfs, int n_cdfs, int cdf_stride, const int32_t *cdf_sizes,
                            const int32_t *offsets) {
-  if (!enc || !cdfs || !cdf_sizes || !offsets || n_cdfs <= 0 || cdf_stride < 2 || (n && (!symbols || !indexes)))
-    return CRA5_ERR_ARG;
-  auto *e = static_cast<BufferedEncoder *>(enc);
   const Tables t{cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets};
+  if (!enc || !tables_ok(t) || (n && (!symbols || !indexes))) return CRA5_ERR_ARG;
+  auto *e = static_cast<BufferedEncoder *>(enc);
   for (size_t i = 0; i < n; ++i) {
-    const int32_t ci = indexes[i];
-    if (ci < 0 || ci >= n_cdfs || cdf_sizes[ci] < 2 || cdf_sizes[ci] > cdf_stride) return CRA5_ERR_INDEX;
-    if (resolve(t, symbols[i], ci).range == 0) return CRA5_ERR_INDEX;   // zero-width bin: nothing is buffered
+    if (!row_ok(t, indexes[i])) return CRA5_ERR_INDEX;
+    if (resolve(t, symbols[i], indexes[i]).range == 0) return CRA5_ERR_INDEX;   // zero-width bin: nothing is buffered
   }
   for (size_t i = 0; i < n; ++i) {
     const Resolved r = resolve(t, symbols[i], indexes[i]);
     e->syms.push_back({static_cast<uint16_t>(r.start), static_cast<uint16_t>(r.range), false});
     if (r.escape) {
-      uint32_t val = static_cast<uint32_t>(r.n_nibbles);
-      while (val >= kBypassMax) {
-        e->syms.push_back({static_cast<uint16_t>(kBypassMax), static_cast<uint16_t>(kBypassMax + 1), true});
-        val -= kBypassMax;
-      }
-      e->syms.push_back({static_cast<uint16_t>(val), static_cast<uint16_t>(val + 1), true});
+      const uint32_t nn = static_cast<uint32_t>(r.n_nibbles);
+      e->syms.push_back({static_cast<uint16_t>(nn), static_cast<uint16_t>(nn + 1), true});
       for (int j = 0; j < r.n_nibbles; ++j) {
         const uint32_t v = (r.raw >> (j * kBypassBits)) & kBypassMax;
         e->syms.push_back({static_cast<uint16_t>(v), static_cast<uint16_t>(v + 1), true});
@@ -640,31 +543,16 @@ int cra5_rans_encoder_push(void *enc, const int32_t *symbols, const int32_t *ind
 int cra5_rans_encoder_flush(void *enc, uint8_t **out, size_t *out_len) {
   if (!enc || !out || !out_len) return CRA5_ERR_ARG;
   auto *e = static_cast<BufferedEncoder *>(enc);
-  const size_t cap = e->syms.size() + 3;   // (+ 1: put() writes one word below the cursor speculatively)
-  uint32_t *buf = static_cast<uint32_t *>(std::malloc(cap * sizeof(uint32_t)));
-  if (!buf) return CRA5_ERR_ALLOC;
-  Encoder c;
-  c.ptr = buf + cap;
-  for (size_t k = e->syms.size(); k-- > 0;) {
-    const BufferedSym &s = e->syms[k];
-    if (!s.bypass) c.put(s.start, s.range);
-    else c.put_bits(s.start);
-  }
-  c.ptr -= 2;
-  c.ptr[0] = static_cast<uint32_t>(c.x);
-  c.ptr[1] = static_cast<uint32_t>(c.x >> 32);
-  const size_t nbytes = static_cast<size_t>((buf + cap) - c.ptr) * sizeof(uint32_t);
-  uint8_t *res = static_cast<uint8_t *>(std::malloc(nbytes));
-  if (!res) {
-    std::free(buf);
-    return CRA5_ERR_ALLOC;
-  }
-  std::memcpy(res, c.ptr, nbytes);
-  std::free(buf);
-  e->syms.clear();
-  *out = res;
-  *out_len = nbytes;
-  return CRA5_OK;
+  const int rc = write_stream(e->syms.size() + 3, [&](Encoder &c) -> int {
+    for (size_t k = e->syms.size(); k-- > 0;) {
+      const BufferedSym &s = e->syms[k];
+      if (!s.bypass) c.put(s.start, s.range);
+      else c.put_bits(s.start);
+    }
+    return CRA5_OK;
+  }, out, out_len);
+  if (rc == CRA5_OK) e->syms.clear();
+  return rc;
 }
 
 /* RansDecoder.set_stream / decode_stream (rans_interface.cpp:286-359): the decoder keeps its
@@ -683,11 +571,11 @@ int cra5_rans_decoder_set_stream(void *dec, const uint8_t *encoded, size_t len) 
 
 int cra5_rans_decoder_decode_stream(void *dec, const int32_t *indexes, size_t n, const int32_t *cdfs, int n_cdfs,
                                     int cdf_stride, const int32_t *cdf_sizes, const int32_t *offsets, int32_t *out) {
-  if (!dec || !cdfs || !cdf_sizes || !offsets || n_cdfs <= 0 || cdf_stride < 2 || (n && (!indexes || !out)))
-    return CRA5_ERR_ARG;
+  const Tables t{cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets};
+  if (!dec || !tables_ok(t) || (n && (!indexes || !out))) return CRA5_ERR_ARG;
   auto *d = static_cast<StreamDecoder *>(dec);
   if (!d->ready) return CRA5_ERR_STREAM;
-  return decode_symbols(d->d, indexes, n, Tables{cdfs, n_cdfs, cdf_stride, cdf_sizes, offsets}, out);
+  return decode_symbols(d->d, indexes, n, t, out);
 }
 
 int cra5_pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *cdf) {

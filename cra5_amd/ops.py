@@ -749,21 +749,36 @@ def _np_i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-def rans_encode(symbols, indexes, cdf, cdf_len, offsets):
-    """-> bytes. Arguments: int32 arrays (numpy or CPU tensors); cdf is [n_cdfs, stride]."""
-    s, i = _np_i32(symbols).reshape(-1), _np_i32(indexes).reshape(-1)
-    c, l, o = _np_i32(cdf), _np_i32(cdf_len).reshape(-1), _np_i32(offsets).reshape(-1)
-    if s.size != i.size:
-        raise ValueError("`symbols` and `indexes` should have the same size.")
-    out = ctypes.c_void_p()
-    n = ctypes.c_size_t()
-    check(lib().cra5_rans_encode_with_indexes(s.ctypes.data, i.ctypes.data, s.size, c.ctypes.data, c.shape[0],
-                                              c.shape[1], l.ctypes.data, o.ctypes.data, ctypes.byref(out),
-                                              ctypes.byref(n)), "cra5_rans_encode_with_indexes")
+def _tables(cdf, cdf_len, offsets):
+    """Host CDF tables as contiguous int32 arrays: cdf [n_cdfs, stride], cdf_len [n_cdfs], offsets [n_cdfs].  cdf may
+    also be a list of (possibly ragged) rows, as the reference's pybind11 module accepts."""
+    if isinstance(cdf, (np.ndarray, torch.Tensor)) and cdf.ndim == 2:
+        c = _np_i32(cdf)
+    else:
+        c = np.zeros((len(cdf), max(len(r) for r in cdf)), dtype=np.int32)
+        for i, r in enumerate(cdf):
+            c[i, : len(r)] = r
+    return c, _np_i32(cdf_len).reshape(-1), _np_i32(offsets).reshape(-1)
+
+
+def _encoded(name, *args):
+    """Calls the native encoder `name`(*args, uint8_t **out, size_t *out_len) -> the malloc'ed stream as bytes."""
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    check(getattr(lib(), name)(*args, ctypes.byref(out), ctypes.byref(n)), name)
     try:
         return ctypes.string_at(out.value, n.value)
     finally:
         lib().cra5_free(out)
+
+
+def rans_encode(symbols, indexes, cdf, cdf_len, offsets):
+    """-> bytes. Arguments: int32 arrays (numpy or CPU tensors); cdf is [n_cdfs, stride]."""
+    s, i = _np_i32(symbols).reshape(-1), _np_i32(indexes).reshape(-1)
+    c, l, o = _tables(cdf, cdf_len, offsets)
+    if s.size != i.size:
+        raise ValueError("`symbols` and `indexes` should have the same size.")
+    return _encoded("cra5_rans_encode_with_indexes", s.ctypes.data, i.ctypes.data, s.size, c.ctypes.data, c.shape[0],
+                   c.shape[1], l.ctypes.data, o.ctypes.data)
 
 
 def rans_resolve_symbols(symbols, indexes, cdf, cdf_len, offsets, out=None):
@@ -796,21 +811,14 @@ def rans_encode_resolved(start_range, raw, esc):
     s, r, e = _np(start_range, np.uint32).reshape(-1), _np(raw, np.uint32).reshape(-1), _np(esc, np.uint8).reshape(-1)
     if not (s.size == r.size == e.size):
         raise ValueError("start_range, raw and esc must have the same size")
-    out = ctypes.c_void_p()
-    n = ctypes.c_size_t()
-    check(lib().cra5_rans_encode_resolved(s.ctypes.data, r.ctypes.data, e.ctypes.data, s.size, ctypes.byref(out),
-                                          ctypes.byref(n)), "cra5_rans_encode_resolved")
-    try:
-        return ctypes.string_at(out.value, n.value)
-    finally:
-        lib().cra5_free(out)
+    return _encoded("cra5_rans_encode_resolved", s.ctypes.data, r.ctypes.data, e.ctypes.data, s.size)
 
 
 def rans_decode(data, indexes, cdf, cdf_len, offsets, out=None):
     """-> int32 numpy array of len(indexes) (written into `out`, a contiguous int32 array of that
     size, when given: e.g. the numpy view of a pinned staging tensor)."""
     i = _np_i32(indexes).reshape(-1)
-    c, l, o = _np_i32(cdf), _np_i32(cdf_len).reshape(-1), _np_i32(offsets).reshape(-1)
+    c, l, o = _tables(cdf, cdf_len, offsets)
     if out is None:
         out = np.empty(i.size, dtype=np.int32)
     elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.size == i.size):
@@ -851,14 +859,7 @@ def rans_encode_resolved_compact(start_range, rec16):
     r_ = np.ascontiguousarray(rec16).view(np.uint16).reshape(-1)
     if s_.size != r_.size:
         raise ValueError("start_range and rec16 must have the same size")
-    out = ctypes.c_void_p()
-    n = ctypes.c_size_t()
-    check(lib().cra5_rans_encode_resolved_compact(s_.ctypes.data, r_.ctypes.data, s_.size, ctypes.byref(out),
-                                                  ctypes.byref(n)), "cra5_rans_encode_resolved_compact")
-    try:
-        return ctypes.string_at(out.value, n.value)
-    finally:
-        lib().cra5_free(out)
+    return _encoded("cra5_rans_encode_resolved_compact", s_.ctypes.data, r_.ctypes.data, s_.size)
 
 
 def rans_decode_compact(data, indexes_u8, cdf, cdf_len, offsets, out):
@@ -869,7 +870,7 @@ def rans_decode_compact(data, indexes_u8, cdf, cdf_len, offsets, out):
         raise ValueError("`indexes_u8` must be a contiguous uint8 numpy array")
     if not (isinstance(out, np.ndarray) and out.dtype == np.int16 and out.flags.c_contiguous and out.size == indexes_u8.size):
         raise ValueError("`out` must be a contiguous int16 numpy array with one entry per index")
-    c, l, o = _np_i32(cdf), _np_i32(cdf_len).reshape(-1), _np_i32(offsets).reshape(-1)
+    c, l, o = _tables(cdf, cdf_len, offsets)
     buf = (ctypes.c_char * len(data)).from_buffer_copy(data)
     check(lib().cra5_rans_decode_with_indexes_u8_i16(ctypes.addressof(buf), len(data), indexes_u8.ctypes.data,
                                                      indexes_u8.size, c.ctypes.data, c.shape[0], c.shape[1],

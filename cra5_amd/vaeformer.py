@@ -329,13 +329,9 @@ class VAEformer(nn.Module):
         # keeps a kernel's tail filled by another frame's blocks without letting ALL frames fall
         # into the host (rANS) phase together, which idles the GPU.  0 = unlimited.
         self.gpu_slots = rc.gpu_slots
-        # Bit-identical implementation alternatives, kept because tests compare the two forms (attributes, no environment
-        # variable): y symbols resolved against the CDF tables by a device kernel (same byte stream) | on the host;
-        # decode side: uint8 CDF indexes / int16 symbols between device and host coder | the int32 records of the
-        # reference's interface; un-embed: GEMM epilogue scatters straight into the reconstruction
-        # (csrc/gemm_split_epilogue_unembed.inc) | GEMM -> column matrix -> overlap-add
-        self.resolve_on_gpu = True
-        self.compact_records = True
+        # un-embed: the GEMM epilogue scatters straight into the reconstruction (csrc/gemm_split_epilogue_unembed.inc) |
+        # GEMM -> column matrix -> overlap-add, the route of the shapes the epilogue does not take (bit-identical; a test
+        # flips the attribute to compare the two)
         self.fused_unembed = True
         self._gpu_sem = None
         # (frames waiting for a GPU-phase slot: encode-side phases first - see _SlotGate; the ~1 ms h_s phase between the
@@ -1034,66 +1030,46 @@ class VAEformer(nn.Module):
         def gpu_side():
             with self._gpu_phase(prio=0):
                 yy = y if y is not None else self._encode_y_frame(x, mean=mean, std=std)
-                if self.resolve_on_gpu and self.compact_records:
-                    # Everything the host phase needs leaves the device as ONE copy (round 5; rounds 1-4: five): the z
-                    # symbols, the y records - symbol -> (start | range, 16-bit escape record) resolved against the CDF
-                    # tables on the device (the host coder is a pure state-update loop, 6 instead of 9 bytes
-                    # per latent cross PCIe) - their overflow word and the finiteness probes of y and of mu / sigma are
-                    # written by their kernels into slices of one per-thread record buffer.
-                    nz, nl = self.entropy_bottleneck.channels * self.Hz * self.Wz, yy.numel()
-                    buf, v, lay = self._pack("enc_pack", [("z_sym", nz, torch.int32), ("sr", nl, torch.int32),
-                                                           ("rec", nl, torch.int16), ("ovf", 1, torch.int32),
-                                                           ("probe", 3 * P, torch.float32)])
-                    s = self._latent_side_frame(yy.contiguous(), z_sym_out=v["z_sym"])
-                    par = self._hs_parent(s["scales"], s["means"])
-                    self._probe(yy, *par, out=v["probe"][:(1 + len(par)) * P])
-                    ops.rans_resolve_symbols_compact(s["y_sym"].reshape(-1), s["idx"].reshape(-1), gc._quantized_cdf,
-                                                     gc._cdf_length, gc._offset, out=(v["sr"], v["rec"], v["ovf"]))
-                    keep["sym"], keep["idx"] = s["y_sym"], s["idx"]   # for the (rare) 32-bit re-resolve
-                    h = self._unpack(self._to_host("enc_pack", buf), lay)
-                    fl = h["probe"][:(1 + len(par)) * P]
-                    z_sym, host = h["z_sym"].view(tuple(s["z_sym"].shape)), ("compact", h["sr"], h["rec"], h["ovf"])
-                else:
-                    s = self._latent_side_frame(yy.contiguous())
-                    par = self._hs_parent(s["scales"], s["means"])
-                    pr = self._probe(yy, *par)          # [y | mu, sigma]: PROBE_PARTIALS values each
-                    z_sym = self._to_host("z_sym", s["z_sym"])
-                    if self.resolve_on_gpu:
-                        sr, raw, esc = ops.rans_resolve_symbols(s["y_sym"].reshape(-1), s["idx"].reshape(-1),
-                                                                gc._quantized_cdf, gc._cdf_length, gc._offset)
-                        host = ("resolved", self._to_host("y_sr", sr), self._to_host("y_raw", raw), self._to_host("y_esc", esc))
-                    else:
-                        host = ("plain", self._to_host("y_sym", s["y_sym"]), self._to_host("idx", s["idx"]))
-                    fl = self._to_host("enc_flags", pr)
-            return (z_sym, host), self._finite(fl[:P]), self._finite(fl[P:])   # (the phase ended with a stream sync)
+                # Everything the host phase needs leaves the device as ONE copy (round 5; rounds 1-4: five): the z
+                # symbols, the y records - symbol -> (start | range, 16-bit escape record) resolved against the CDF
+                # tables on the device (the host coder is a pure state-update loop, 6 instead of 9 bytes
+                # per latent cross PCIe) - their overflow word and the finiteness probes of y and of mu / sigma are
+                # written by their kernels into slices of one per-thread record buffer.
+                nz, nl = self.entropy_bottleneck.channels * self.Hz * self.Wz, yy.numel()
+                buf, v, lay = self._pack("enc_pack", [("z_sym", nz, torch.int32), ("sr", nl, torch.int32),
+                                                       ("rec", nl, torch.int16), ("ovf", 1, torch.int32),
+                                                       ("probe", 3 * P, torch.float32)])
+                s = self._latent_side_frame(yy.contiguous(), z_sym_out=v["z_sym"])
+                par = self._hs_parent(s["scales"], s["means"])
+                self._probe(yy, *par, out=v["probe"][:(1 + len(par)) * P])
+                ops.rans_resolve_symbols_compact(s["y_sym"].reshape(-1), s["idx"].reshape(-1), gc._quantized_cdf,
+                                                 gc._cdf_length, gc._offset, out=(v["sr"], v["rec"], v["ovf"]))
+                keep["sym"], keep["idx"] = s["y_sym"], s["idx"]   # for the (rare) 32-bit re-resolve
+                h = self._unpack(self._to_host("enc_pack", buf), lay)
+                fl = h["probe"][:(1 + len(par)) * P]
+            return (h["z_sym"].view(tuple(s["z_sym"].shape)), h), self._finite(fl[:P]), self._finite(fl[P:])   # (the phase ended with a stream sync)
         keep = {}
-        z_sym, host = self._range_guard(0, gpu_side, "compress")
+        z_sym, h = self._range_guard(0, gpu_side, "compress")
         t_host = time.perf_counter()
         # the z stream is coded beside the y stream (round 6): two independent coders, the native calls release the GIL -
         # 2 ms off the serial host phase of every frame (16.5 ms with the default synthetic weights, 8.5 entropy-matched)
         z_job = self._z_pool().submit(self._encode_z, z_sym.numpy().reshape(-1), (1, z_sym.shape[0], z_sym.shape[1]))   # (joined below)
         try:
-            if host[0] == "compact" and int(host[3][0]) != 0:
+            if int(h["ovf"][0]) == 0:
+                keep.clear()
+                rec_np = h["rec"].numpy()
+                y_str = ops.rans_encode_resolved_compact(h["sr"].numpy(), rec_np)
+                n_esc = int(np.count_nonzero(rec_np))
+            else:
                 # an escape payload beyond 12 bits (|symbol| thousands beyond its table row): this frame takes the 32-bit records
                 with self._gpu_phase(light=True):
                     sr, raw, esc = ops.rans_resolve_symbols(keep["sym"].reshape(-1), keep["idx"].reshape(-1),
                                                             gc._quantized_cdf, gc._cdf_length, gc._offset)
-                    host = ("resolved", self._to_host("y_sr", sr), self._to_host("y_raw", raw), self._to_host("y_esc", esc))
-            keep.clear()
-            if host[0] == "compact":
-                rec_np = host[2].numpy()
-                y_str = ops.rans_encode_resolved_compact(host[1].numpy(), rec_np)
-                n_esc = int(np.count_nonzero(rec_np))
-            elif host[0] == "resolved":
-                esc_np = host[3].numpy()
-                y_str = ops.rans_encode_resolved(host[1].numpy(), host[2].numpy(), esc_np)
+                    sr, raw, esc = self._to_host("y_sr", sr), self._to_host("y_raw", raw), self._to_host("y_esc", esc)
+                keep.clear()
+                esc_np = esc.numpy()
+                y_str = ops.rans_encode_resolved(sr.numpy(), raw.numpy(), esc_np)
                 n_esc = int(np.count_nonzero(esc_np))
-            else:
-                sym_np, idx_np = host[1].numpy().reshape(-1), host[2].numpy().reshape(-1)
-                y_str = gc.encode_symbols(sym_np, idx_np)
-                _, ln, off = gc.host_tables()
-                v = sym_np - off[idx_np]
-                n_esc = int(np.count_nonzero((v < 0) | (v >= ln[idx_np] - 2)))
         except BaseException:
             z_job.cancel()
             try:
@@ -1175,7 +1151,7 @@ class VAEformer(nn.Module):
             z_hat = ops.entropy_bottleneck(med, None, sym_in=z_sym, want=("z_hat",))["z_hat"]
             scales, means = self._h_s_frame(z_hat)
             scales, means = scales.contiguous(), means.contiguous()
-            compact = self.compact_records and gc.scale_table.numel() <= 256
+            compact = gc.scale_table.numel() <= 256
             par = self._hs_parent(scales, means)
             if compact:
                 # compact records (round 4): uint8 CDF indexes to the host, int16 symbols back - 8 instead of 21 MB of

@@ -63,7 +63,8 @@ int cra5_rans_encode_resolved(const uint32_t *start_range, const uint32_t *raw, 
                               uint8_t **out, size_t *out_len);
 /* The same on COMPACT records (6 instead of 9 bytes per latent between device and host): rec16[i] = 0 for a regular
  * symbol, (1 + payload nibbles) << 12 | payload for an escape whose payload fits 12 bits; a record 0xFFFF (payload
- * beyond 12 bits / invalid index) returns CRA5_ERR_RANGE - encode from the 32-bit records then.  Same bytes. */
+ * beyond 12 bits / invalid index) returns CRA5_ERR_RANGE - encode from the 32-bit records then; a record with payload
+ * bits above its nibble count returns CRA5_ERR_INDEX.  Same bytes. */
 int cra5_rans_encode_resolved_compact(const uint32_t *start_range, const uint16_t *rec16, size_t n, uint8_t **out,
                                       size_t *out_len);
 

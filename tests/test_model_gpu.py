@@ -939,22 +939,21 @@ def test_frame_pipeline_scheduling_is_transparent(thin, dev):
         pipe.close()
 
 
-def test_gpu_resolved_encoder_same_stream(thin, big, dev):
-    """Resolving the y symbols against the CDF tables on the device (cra5_rans_resolve_symbols_i32 +
-    cra5_rans_encode_resolved) writes exactly the stream of the table-driven host encoder, on the thin
-    model and on the full-size one (escape-heavy: half of its symbols sit in the narrowest row)."""
+def test_frame_path_streams_equal_the_table_driven_host_encoders(thin, big, dev):
+    """The frame path resolves the y symbols against the CDF tables on the device (compact records +
+    cra5_rans_encode_resolved_compact) and writes exactly the streams of the table-driven host encoders on the same
+    frame's integers, on the thin model and on the full-size one (escape-heavy: half of its symbols sit in the
+    narrowest row)."""
     for net, C in ((thin, thin.cfg['in_chans']), (big, 268)):
         x = synth.synth_frame(C, seed=11).unsqueeze(0).to(dev)
-        keep = net.resolve_on_gpu
-        try:
-            net.resolve_on_gpu = True
-            a = net.compress(x)
-            net.resolve_on_gpu = False
-            b = net.compress(x)
-        finally:
-            net.resolve_on_gpu = keep
-        assert a["strings"][0][0] == b["strings"][0][0] and a["strings"][1][0] == b["strings"][1][0]
-        assert len(a["strings"][0][0]) > 1000
+        a = net.compress(x)
+        s = net._latent_side_guarded(net._encode_y_guarded(x[0]))
+        z_sym = s["z_sym"].cpu().numpy()
+        y_str = net.gaussian_conditional.encode_symbols(s["y_sym"].cpu().numpy().reshape(-1),
+                                                        s["idx"].cpu().numpy().reshape(-1))
+        assert a["strings"][0][0] == y_str
+        assert a["strings"][1][0] == net._encode_z(z_sym.reshape(-1), (1, z_sym.shape[0], z_sym.shape[1]))
+        assert len(y_str) > 1000
 
 
 def test_rate_estimate_predicts_stream_size(thin, dev):
@@ -1173,7 +1172,7 @@ def test_range_guard_decode_side_and_pinned_hyper_path(dev):
 
 
 def test_compact_records_device_kernels_match_the_32_bit_ones(thin, thin_side, dev):
-    """resolve_symbols_compact_kernel / gaussian_conditional_compact_kernel against the int32 kernels they shadow, on a
+    """resolve_symbols_kernel<CompactRecords> / gaussian_conditional_compact_kernel against the int32 kernels they shadow, on a
     real frame's integers."""
     _, y, s = thin_side
     gc = thin.gaussian_conditional
@@ -1194,32 +1193,30 @@ def test_compact_records_device_kernels_match_the_32_bit_ones(thin, thin_side, d
     assert torch.equal(yh.reshape(-1), s["y_hat"].reshape(-1))
 
 
-def test_compact_records_same_streams_and_reconstruction_incl_the_32_bit_fallback(thin, thin_side, dev):
+def test_compact_records_match_the_host_coder_incl_the_32_bit_fallback(thin, thin_side, dev):
+    """The frame path's compact records write the table-driven host encoder's stream, and the int32 decoder reads the
+    symbols the model's decode reconstructs from - also for a frame whose escape payloads exceed 12 bits / whose symbols
+    exceed int16 (both sides then take the 32-bit records for that frame)."""
     x, y, s = thin_side
-    assert thin.compact_records
-    out_c = thin.compress(x)
-    rec_c = thin.decompress(out_c["strings"], out_c["z_shape"])["x_hat"]
-    thin.compact_records = False
-    try:
-        out_w = thin.compress(x)
-        rec_w = thin.decompress(out_c["strings"], out_c["z_shape"])["x_hat"]
-    finally:
-        thin.compact_records = True
-    assert out_c["strings"] == out_w["strings"] and torch.equal(rec_c, rec_w)
+    gc = thin.gaussian_conditional
+
+    def check(out, side):
+        sym, idx = side["y_sym"].cpu().numpy().reshape(-1), side["idx"].cpu().numpy().reshape(-1)
+        assert out["strings"][0][0] == gc.encode_symbols(sym, idx)
+        assert np.array_equal(gc.decode_symbols(out["strings"][0][0], idx), sym)
+        y_hat = thin.decompress(out["strings"], out["z_shape"], return_format='latent')
+        assert torch.equal(y_hat[0].reshape(-1), side["y_hat"].reshape(-1))
+        return y_hat
+
+    check(thin.compress(x), s)
     assert thin.last_n_escape()[0] > 0
     # a latent with symbols far outside every table row (escape payloads beyond 12 bits on the encode side, symbols beyond
     # int16 on the decode side): both sides fall back to the 32-bit records for that frame, the round trip stays exact
     y_big = y.clone()
     y_big[0, 3, 10, 20] += 40000.0          # (inside the f16 range of the h_a input split: no poison, only huge symbols)
     y_big[0, 5, 11, 21] -= 40000.0
-    out_b = thin.compress_from_latent(y_big)
-    y_hat = thin.decompress(out_b["strings"], out_b["z_shape"], return_format='latent')
-    thin.compact_records = False
-    try:
-        out_b32 = thin.compress_from_latent(y_big)
-        y_hat32 = thin.decompress(out_b["strings"], out_b["z_shape"], return_format='latent')
-    finally:
-        thin.compact_records = True
-    assert out_b["strings"] == out_b32["strings"] and torch.equal(y_hat, y_hat32)
+    s_big = thin._latent_side_guarded(y_big[0])
+    assert int(s_big["y_sym"].abs().max()) > 32767
+    y_hat = check(thin.compress_from_latent(y_big), s_big)
     assert abs(float(y_hat[0, 3, 10, 20] - y_big[0, 3, 10, 20])) <= 0.5 + 1e-3
     assert abs(float(y_hat[0, 5, 11, 21] - y_big[0, 5, 11, 21])) <= 0.5 + 1e-3

@@ -399,6 +399,21 @@ def test_compact_records_write_and_read_the_same_streams(seed):
     assert np.array_equal(ops.rans_decode(big_stream, idx, cdf, lens, offs), sym_big)     # the 32-bit route reads it
 
 
+def test_compact_record_with_payload_bits_above_its_nibble_count_is_refused():
+    """cra5_rans_encode_resolved_compact codes a record's payload as exactly its declared nibbles: a record with payload
+    bits above them is malformed (the device resolver never writes one) and returns CRA5_ERR_INDEX instead of ORing the
+    stray bits into the coder state."""
+    sr = np.full(4, 4096 << 16, dtype=np.uint32)      # start 0, range 4096
+    good = np.array([0, (1 + 1) << 12 | 0x5, (1 + 2) << 12 | 0x5A, (1 + 3) << 12 | 0xFFF], dtype=np.uint16)
+    assert len(ops.rans_encode_resolved_compact(sr, good)) >= 8
+    for bad in ((1 + 0) << 12 | 0x1, (1 + 1) << 12 | 0x10, (1 + 2) << 12 | 0x100):
+        rec = good.copy()
+        rec[2] = bad
+        with pytest.raises(Cra5Error) as ei:
+            ops.rans_encode_resolved_compact(sr, rec)
+        assert ei.value.status == -2, hex(bad)      # CRA5_ERR_INDEX
+
+
 # ---- round 6: a desynchronised stream is an error, not a picture (VERDICT r5 item 4) -----------------------------------
 # rans_interface.cpp:215-284 (the reference's decoder) hands back whatever symbols fall out of a stream decoded with
 # indexes that are not the encoder's; the product's one-shot decoders check that the coder is back at RANS64_L with every
