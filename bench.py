@@ -15,12 +15,16 @@ is no network for the checkpoint / ERA5 samples).  Frames shard over ranks with 
 data-path collective (weak scaling: one frame per rank per step); the only exchange is
 the RCCL all-gather of per-frame bitstream stats after the timed region.
 
-Prints ONE JSON line (rank 0) with the driver contract fields plus
-  "roofline":     achieved fp32 MFMA TFLOP/s of the dominant kernel (gemm_nt_f32), timed
-                  with HIP events on the launch stream over the timed region;
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints ONE JSON line (rank 0) with the
+driver contract fields and what the timed region itself recorded (stream stats, shader clock, sampled kernel timer).
+--full adds everything that needs work of its own after the timed region (rank 0, N = 1 unless noted):
+  "roofline":     achieved fp32-equivalent TFLOP/s of the big-tile GEMM, HIP events around every launch of an
+                  un-overlapped pass (every N), and the kernel on its best-case shape;
+  "precision_f16", "api_single_frame", "entropy_matched", "api_pipelined": the same frames through the
+                  reduced-precision mode, the reference-named API and the entropy-matched weights;
+  "reference_pinned_frames": frames 0 / 1 against the streams the reference's Python wrote (every N);
   "cpu_baseline": the CPU oracle (oracle/torch_ref.py = restatement of the reference's
-                  math path + oracle C rANS) timed on this box's host cores on a bounded
-                  sample (rank 0, N = 1 only).
+                  math path + oracle C rANS) on this box's host cores.
 
 --dump-outputs DIR writes what the last timed step returned (rank 0) as float32 DIR/<name>.npy, at most 64 MB: the y / z
 streams and z_shape in full and a fixed seeded sample of x_hat.  The same arguments give the same inputs (seeded frames
@@ -699,6 +703,12 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed region, write what the last timed step returned (rank 0) as DIR/<name>.npy: "
                          "the y / z streams and z_shape in full, a fixed seeded sample of x_hat (dump_outputs())")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs that need work of their own: the un-overlapped roofline "
+                         "pass (--roofline-steps, --no-best-case), the reduced-precision, API and entropy-matched samples "
+                         "(--no-f16-sample, --no-api-sample, --api-frames, --no-matched-sample), the reference-pinned "
+                         "frames and the CPU baseline (--cpu-baseline, --no-cpu-baseline); off: the line carries only what "
+                         "the timed region measured")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -967,9 +977,6 @@ def main():
         "per_rank": per_rank,
         "clocks": clocks,
         "host_phase_ms": host_phase_summary(host_log),
-        # frames 0 / 1 of the job (rank 0 owns them): product stream vs the stream the reference's Python wrote for the same tensor
-        "reference_pinned_frames": {str(1000 + f): reference_pinned(1000 + f, results[i][0]["strings"])
-                                    for i, f in enumerate(my_frames) if f < 2 and i < pool} or None,
         "collectives": {"initialized": bool(torch.distributed.is_available() and torch.distributed.is_initialized()),
                         "backend": (torch.distributed.get_backend() if torch.distributed.is_initialized() else None),
                         "data_path": "none (frames are independent)", "after_timed_region": "all_gather of int64[K,5] stats"},
@@ -985,6 +992,11 @@ def main():
             (PEAK_FP32_MFMA_TFLOPS if net.gemm_mode == "f32" else
              PEAK_F16_MFMA_TFLOPS / (3.0 if net.precision == "fp32" else 1.0)) * 1e12),
     }
+    if args.full:
+        # frames 0 / 1 of the job (rank 0 owns them): product stream vs the stream the reference's Python wrote for the same tensor
+        result["reference_pinned_frames"] = {str(1000 + f): reference_pinned(1000 + f, results[i][0]["strings"])
+                                             for i, f in enumerate(my_frames) if f < 2 and i < pool} or None
+
     def measured_traffic():
         """HBM-side bytes per gemm launch from the committed rocprofv3 PMC passes (FETCH_SIZE
         x2 + WRITE_SIZE, corrected as MI355X_MICROARCH.md prescribes); PMC collection needs its
@@ -1087,10 +1099,11 @@ def main():
         timed = roofline_from(timer.summary(), args.steps, args.timer_sample)
         # In the timed region only every n-th launch is bracketed (and, in the default mode, launches of
         # concurrent frames overlap, so start->stop of one launch also contains other frames' kernels).
-        # Keep those numbers, and time EVERY launch of the same kernels un-overlapped in a short extra
+        # Keep those numbers, and (--full) time EVERY launch of the same kernels un-overlapped in a short extra
         # pass outside the timed region.
         result["roofline_timed_region"] = timed.get("roofline")
         result["attention_timed_region"] = timed.get("attention")
+    if timer is not None and args.full:
         net.gpu_exclusive = True
         ops.TIMER = t2 = ops.KernelTimer()
         pipe.roundtrip([frames[i % pool] for i in range(max(1, args.roofline_steps))])
@@ -1144,7 +1157,9 @@ def main():
                 "region (HIP events around every launch, on the launch stream, exclusive GPU phases); "
                 "`roofline_timed_region` holds the sampled measurement taken inside the timed region, where "
                 "launches of concurrent frames overlap and per-launch durations are inflated")
-    if rank == 0 and world == 1 and args.precision == "fp32" and not args.no_f16_sample and args.quality == 268 \
+    # the legs below run on rank 0 of a 1-rank job, with --full only
+    side_legs = rank == 0 and world == 1 and args.full
+    if side_legs and args.precision == "fp32" and not args.no_f16_sample and args.quality == 268 \
             and net.gemm_mode != "f32":
         # BASELINE.json configs[4] (reduced precision: plain f16 operands in g_a / g_s, fp32 accumulate, hyper-prior and
         # GaussianConditional fp32-accurate) on THIS GPU: a short sample outside the timed region - frames/s of the same
@@ -1183,7 +1198,7 @@ def main():
             result["precision_f16"] = {"value": None, "error": repr(ex)}
         finally:
             net.precision = "fp32"
-    if rank == 0 and world == 1 and not args.no_api_sample and args.quality == 268:
+    if side_legs and not args.no_api_sample and args.quality == 268:
         # What a drop-in caller of the REFERENCE-NAMED single-frame methods sees (test.py:14-45 in the reference):
         # encode_era5_as_bin(host array -> .bin on disk) + decode_from_bin(.bin -> x_hat on the device), one frame at
         # a time on one thread, PCIe-inclusive.  Outside the timed region; never part of `value`.
@@ -1229,7 +1244,7 @@ def main():
             shutil.rmtree(tmp, ignore_errors=True)
         except Exception as ex:  # noqa: BLE001
             result["api_single_frame"] = {"value": None, "error": repr(ex)}
-    if rank == 0 and world == 1 and not args.no_matched_sample and args.quality == 268 and args.precision == "fp32":
+    if side_legs and not args.no_matched_sample and args.quality == 268 and args.precision == "fp32":
         try:
             result["entropy_matched"] = matched_sample(
                 net, pipe, frames, max(20, 2 * args.inflight),
@@ -1237,12 +1252,12 @@ def main():
                  "escape_symbols_per_frame": result["escape_symbols_per_frame"], "host_phase_ms": result["host_phase_ms"]})
         except Exception as ex:  # noqa: BLE001
             result["entropy_matched"] = {"value": None, "error": repr(ex)}
-    if rank == 0 and world == 1 and not args.no_api_sample and args.quality == 268:
+    if side_legs and not args.no_api_sample and args.quality == 268:
         try:
             result["api_pipelined"] = api_pipelined_sample(net, pipe, frames, args.inflight, args.api_frames)
         except Exception as ex:  # noqa: BLE001
             result["api_pipelined"] = {"value": None, "error": repr(ex)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if side_legs and not args.no_cpu_baseline:
         # The reference's CPU path on THIS box's host cores, in THIS run, after every GPU leg so that a
         # host busy with the oracle cannot touch `value`.  The pipeline's frame threads are idle by now; the NUMA bind of
         # the GPU legs is lifted (the oracle gets every core of the box, as a CPU user of the reference would have).

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def bench_line():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
            "--settle-batches", "0", "--roofline-steps", "1", "--no-cpu-baseline", "--api-frames", "12"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, stdin=subprocess.DEVNULL)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -69,6 +69,28 @@ def test_bench_json_contract(bench_line):
     pin = d["reference_pinned_frames"]
     assert pin and set(pin) == {"1000", "1001"} and all(v["z_bytes"] == v["z_bytes_reference"] for v in pin.values())
     assert all(abs(v["y_bytes"] - v["y_bytes_reference"]) <= 256 for v in pin.values())
+
+
+FULL_ONLY = ("roofline", "attention", "hbm_bound_kernels", "precision_f16", "api_single_frame", "entropy_matched", "api_pipelined",
+             "cpu_baseline", "reference_pinned_frames")
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_leaves_the_full_legs_out():
+    """Without --full the run ends at the timed region: the contract fields and what the region recorded (sampled kernel
+    timer, clocks, stream stats), none of the legs that need work of their own."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--settle-batches", "0"]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, stdin=subprocess.DEVNULL)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out_lines = [l for l in p.stdout.strip().split("\n") if l.strip()]
+    assert len(out_lines) == 1 and out_lines[0].startswith("{"), out_lines[:3]
+    d = json.loads(out_lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    assert d["dtype"] == "f32 (3xf16-split MFMA, fp32 accumulate)" and d["higher_is_better"] is True
+    assert d["roofline_timed_region"]["launches"] > 0 and d["determinism_check"]["repeated_frames_with_identical_streams_rank0"] >= 1
+    assert not set(FULL_ONLY) & set(d), sorted(set(FULL_ONLY) & set(d))
 
 
 @pytest.mark.gpu

@@ -7,7 +7,7 @@ T=${1:-r05}
 O=$R/gpurun_out/$T
 mkdir -p $O
 COMMON="--precision f16 --no-cpu-baseline --no-api-sample --no-f16-sample --no-best-case --no-matched-sample"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_f16 -o bench -- python $R/bench.py --steps 16 --warmup 4 --exclusive $COMMON > $O/bench_f16_excl.log 2>&1 < /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_f16 -o bench -- python $R/bench.py --full --steps 16 --warmup 4 --exclusive $COMMON > $O/bench_f16_excl.log 2>&1 < /dev/null
 cp $(find $O/prof_f16 -name '*kernel_stats.csv' | head -1) $O/${T}_f16_bench_exclusive_kernel_stats.csv
 grep -h '"metric"' $O/bench_f16_excl.log | tail -1 > $O/${T}_f16_bench_exclusive.json
 rm -rf $O/prof_f16
