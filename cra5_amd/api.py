@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import binfmt, ops
+from .config import RuntimeConfig, runtime_setting
 from .zoo import vaeformer_pretrained
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,24 +57,25 @@ class cra5_api:
         self._std_flat = self.std.reshape(-1).contiguous()
         self.channels_to_vname, self.vname_to_channels = self.channel_vname_mapping()
         self.local_root = local_root or f'{os.getcwd()}/data'
-        # batch methods: host threads per frame copy between pageable and pinned memory (1 = one numpy copy on the frame thread)
-        from .config import RuntimeConfig
+        # settings: ONE RuntimeConfig (cra5_amd/config.py); batch_copy_threads / link_serial are properties over it
         self.runtime = runtime if runtime is not None else (getattr(weights, "runtime", None) or RuntimeConfig.from_env())
-        self.batch_copy_threads = self.runtime.batch_copy_threads
-        # batch methods: ONE frame per direction on the host link at a time (round 6).  Twelve frame threads that all
-        # issue their 1.11 GB H2D at once share the link - every frame lands after 12 transfer times, the GPU idles
-        # until then and the frames then queue for it in a convoy; one at a time, the first frame lands after one
-        # transfer time and the GPU starts while the next frame is on the wire.  The link itself runs 57 GB/s in either
-        # direction and 97 GB/s both ways at once (profiles/r06_link_probe.txt), so H2D and D2H get a gate each.
         import threading
-        self.link_serial = self.runtime.link_serial
         self._link_gate = {"h2d": threading.Lock(), "d2h": threading.Lock()}
         self.phase_log = None       # a list: (frame tag, phase, t_start, t_end) per batch-path phase (tools/api_phase_probe.py)
         self._era5 = None
         if weights is not None:
             self.net = weights.eval().to(self.device)
         else:
-            self.net = vaeformer_pretrained(quality=quality, pretrained=True).eval().to(self.device)
+            self.net = vaeformer_pretrained(quality=quality, pretrained=True, runtime=self.runtime).eval().to(self.device)
+
+    # batch methods: host threads per frame copy between pageable and pinned memory (1 = one numpy copy on the frame thread)
+    batch_copy_threads = runtime_setting("batch_copy_threads")
+    # batch methods: ONE frame per direction on the host link at a time (round 6).  Twelve frame threads that all issue
+    # their 1.11 GB H2D at once share the link - every frame lands after 12 transfer times, the GPU idles until then and
+    # the frames then queue for it in a convoy; one at a time, the first frame lands after one transfer time and the GPU
+    # starts while the next frame is on the wire.  The link itself runs 57 GB/s in either direction and 97 GB/s both ways
+    # at once (profiles/r06_link_probe.txt), so H2D and D2H get a gate each.
+    link_serial = runtime_setting("link_serial")
 
     # ------------------------------------------------------------------ ingest
     def download_era5_data(self, time_stamp=None, save_root=None, data_formate="nc"):

@@ -2,8 +2,14 @@
 
 Everything a deployment may want to set is a field of `RuntimeConfig`; `RuntimeConfig.from_env()` is the only code of the
 package that turns `CRA5_*` variables into settings ("model config as a dataclass"; VERDICT r5 item
-8).  `VAEformer(..., runtime=cfg)` / `cra5_api(..., runtime=cfg)` take an explicit object; without one they call
-`from_env()`.  bench.py prints `describe()` into its JSON line.
+8).  `VAEformer(..., runtime=cfg)`, `vaeformer_pretrained(..., runtime=cfg)` (its `weights` names the checkpoint) and
+`cra5_api(..., runtime=cfg)` take an explicit object; without one they call `from_env()`.  bench.py prints `describe()`
+into its JSON line.
+
+The object a model / API holds as `.runtime` is the only store of its settings: their attributes (`VAEformer.precision`,
+`.gemm_mode`, `.attn_mode`, `.range_guard`, `.gpu_exclusive`, `.gpu_slots`; `cra5_api.batch_copy_threads`,
+`.link_serial`) are properties over it (`runtime_setting`), and assigning one replaces `.runtime` with a validated copy -
+the caller's object is never mutated.
 
 Not settings, and therefore not here:
   * the ARCHITECTURE (`cra5_amd.vaeformer.config_for`: the reference's ddconfig / priorconfig dictionaries);
@@ -85,4 +91,15 @@ class RuntimeConfig:
         d = dataclasses.asdict(self)
         d["set_by_environment"] = sorted(v for k, v in self.ENV.items() if v in os.environ)
         return d
+
+
+def runtime_setting(field):
+    """Class attribute: a property that reads `self.runtime.<field>`; assigning it replaces `self.runtime` with a copy
+    holding the new value, so `RuntimeConfig.__post_init__` validates it."""
+    def get(self):
+        return getattr(self.runtime, field)
+
+    def set_(self, v):
+        self.runtime = self.runtime.replace(**{field: v})
+    return property(get, set_)
 

@@ -29,7 +29,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import ERR_RANGE, Cra5Error, StreamDesyncError
-from .config import RuntimeConfig
+from .config import RuntimeConfig, runtime_setting
 from .entropy import EntropyBottleneck, GaussianConditional, get_scale_table
 
 __all__ = ["VAEformer", "config_for", "block_windows"]
@@ -290,33 +290,24 @@ class VAEformer(nn.Module):
         self.h_s = _Decoder(hd, hh, [None] * (cfg['h_depth'] - n_h),
                             _Linear(hd, 2 * cfg['h_in_chans'] * zh * zw, bias=False), cfg['z_dim'])
         self.gaussian_conditional = GaussianConditional(None)
-        # GPU phases of concurrent frames: exclusive (one frame's kernels at a time) or shared
-        # (streams overlap: other frames' blocks fill the tail / epilogue gaps of a kernel)
         # Runtime settings: ONE RuntimeConfig object (cra5_amd/config.py), from the caller (`runtime=`) or from the
-        # environment - the only place of the package that reads CRA5_* settings.  The attributes below are its fields,
-        # kept as plain attributes so that a caller / bench.py can change them between frames.
+        # environment - the only place of the package that reads CRA5_* settings.  `precision`, `gemm_mode`, `attn_mode`,
+        # `range_guard`, `gpu_exclusive` and `gpu_slots` are properties over it; assigning one replaces the object
+        # (config.runtime_setting), so a caller / bench.py can change them between frames and RuntimeConfig validates
+        # every value.
         rc = kwargs.pop("runtime", None)
-        self.runtime = rc = rc if rc is not None else RuntimeConfig.from_env()
-        self.gpu_exclusive = rc.gpu_exclusive
-        self._attn_mode = rc.attn_engine   # "split" (f16-MFMA, fp32-accurate) | "f32"
+        self.runtime = rc if rc is not None else RuntimeConfig.from_env()
         # whole-grid attention: balanced 12-wave passes + key-split leftover (csrc/attention_split_f16.hip, BAL); False keeps
         # the plain 27-work-groups-per-head launch (a bit-identical-on-full-tiles alternative: tests flip the attribute)
         self.attn_balanced = True
-        self._gemm_mode = rc.gemm_engine
         # range guard (csrc/split.h): frames whose split-f16 activations left the f16 range are re-run on the exact-f32
         # engines; counted here (encode side, decode side); range_guard False turns the re-run into an error
         self.range_fallbacks = [0, 0]
-        self.range_guard = rc.range_guard
-        # "fp32" (default): 3-product split, fp32-accurate.  "f16": BASELINE.json configs[4] -
-        # g_a / g_s projections and attention use plain f16 operands (1 MFMA per product, fp32
-        # accumulate); the hyper-prior / GaussianConditional side stays fp32-accurate so that
-        # encoder and decoder derive identical CDF indexes.  RMSE-gated in tests/test_model_gpu.py.
         # optional timeline of the GPU phases: a list receives (thread id, t_request, t_start, t_end)
         # per phase (tools/phase_timeline.py); None = off
         self.phase_log = None
         # optional log of the host (rANS) phases: a list receives ("enc" | "dec_z" | "dec_y", seconds) per frame; None = off
         self.host_log = None
-        self.precision = rc.precision
         # reduced-precision mode: "plain" (round 5) - activations and weights of g_a / g_s travel as PLAIN f16 rows wherever
         # the consuming kernel takes them (full 128-byte lines per k-step: -13..-18 % per GEMM launch, bit-identical
         # results); "split" keeps the hi planes of split rows (rounds 1-4; a test flips the attribute)
@@ -325,10 +316,6 @@ class VAEformer(nn.Module):
         self._derive_lock = threading.RLock()
         self._gpu_lock = threading.Lock()
         self._fallback_lock = threading.Lock()     # range-guard re-runs on the exact-f32 engines: one frame at a time
-        # gpu_slots = n > 0: at most n frames inside a GPU phase at a time (shared-stream mode only):
-        # keeps a kernel's tail filled by another frame's blocks without letting ALL frames fall
-        # into the host (rANS) phase together, which idles the GPU.  0 = unlimited.
-        self.gpu_slots = rc.gpu_slots
         # un-embed: the GEMM epilogue scatters straight into the reconstruction (csrc/gemm_split_epilogue_unembed.inc) |
         # GEMM -> column matrix -> overlap-add, the route of the shapes the epilogue does not take (bit-identical; a test
         # flips the attribute to compare the two)
@@ -341,28 +328,39 @@ class VAEformer(nn.Module):
         self._tls = threading.local()  # per-thread workspaces: one frame pipeline per thread/stream
         self.eval()
 
+    # ---- runtime settings: properties over self.runtime (config.runtime_setting) ---------------------------------
+    # "fp32" (default): 3-product split, fp32-accurate.  "f16": BASELINE.json configs[4] - g_a / g_s projections and
+    # attention use plain f16 operands (1 MFMA per product, fp32 accumulate); the hyper-prior / GaussianConditional side
+    # stays fp32-accurate so that encoder and decoder derive identical CDF indexes.  RMSE-gated in tests/test_model_gpu.py.
+    precision = runtime_setting("precision")
+    range_guard = runtime_setting("range_guard")
+    # GPU phases of concurrent frames: exclusive (one frame's kernels at a time) or shared (streams overlap: other frames'
+    # blocks fill the tail / epilogue gaps of a kernel)
+    gpu_exclusive = runtime_setting("gpu_exclusive")
+    # gpu_slots = n > 0: at most n frames inside a GPU phase at a time (shared-stream mode only): keeps a kernel's tail
+    # filled by another frame's blocks without letting ALL frames fall into the host (rANS) phase together, which idles
+    # the GPU.  0 = unlimited.  (_gpu_phase rebuilds its _SlotGate when the value changes.)
+    gpu_slots = runtime_setting("gpu_slots")
 
     # ---- engines: model-wide setting, overridable per thread (the range guard re-runs ONE frame on the exact-f32
     # engines while the other frame threads of the pipeline keep the split engines) ------------------------------
     @property
     def gemm_mode(self):
         o = getattr(self._tls, "engine_override", None)
-        return o if o is not None else self._gemm_mode
+        return o if o is not None else self.runtime.gemm_engine
 
     @gemm_mode.setter
     def gemm_mode(self, v):
-        if v not in ("split", "f32"):
-            raise ValueError("gemm_mode must be 'split' or 'f32'")
-        self._gemm_mode = v
+        self.runtime = self.runtime.replace(gemm_engine=v)
 
     @property
     def attn_mode(self):
         o = getattr(self._tls, "engine_override", None)
-        return o if o is not None else self._attn_mode
+        return o if o is not None else self.runtime.attn_engine
 
     @attn_mode.setter
     def attn_mode(self, v):
-        self._attn_mode = v
+        self.runtime = self.runtime.replace(attn_engine=v)
 
     @contextlib.contextmanager
     def _exact_f32_engines(self):
@@ -398,6 +396,12 @@ class VAEformer(nn.Module):
     def _finite(host_values):
         return bool(torch.isfinite(host_values).all())
 
+    @staticmethod
+    def _hyper_nonfinite(what, cause):
+        """The error of a non-finite mu / sigma: the hyper-prior engine is pinned, a re-run would give the same values."""
+        return FloatingPointError(f"{what}: the hyper-prior path produced non-finite entropy parameters (its engine is "
+                                  f"pinned on both sides of the codec, there is no fallback): {cause}")
+
     def _range_guard(self, side, run, what):
         """Run one frame's GPU work `run()` -> (result, finite flag [device bool], hyper flag or None).  A non-finite
         result means a split-f16 store left the f16 range (csrc/split.h poisons it) or the input itself was non-finite:
@@ -408,8 +412,7 @@ class VAEformer(nn.Module):
         if bool(ok) and (ok_h is None or bool(ok_h)):
             return res
         if ok_h is not None and bool(ok) and not bool(ok_h):
-            raise FloatingPointError(f"{what}: the hyper-prior path produced non-finite entropy parameters (its engine is "
-                                     "pinned on both sides of the codec, there is no fallback): check the checkpoint")
+            raise self._hyper_nonfinite(what, "check the checkpoint")
         if self.gemm_mode == "f32" or not self.range_guard:
             raise FloatingPointError(f"{what}: non-finite values on the device (" + (
                 "exact-f32 engines: the input or the weights are non-finite" if self.gemm_mode == "f32" else
@@ -435,13 +438,13 @@ class VAEformer(nn.Module):
 
     # ---- reference-compatible loading (vaeformer.py:168-185, base.py:69-89) -------------
     @classmethod
-    def from_state_dict(cls, state_dict):
+    def from_state_dict(cls, state_dict, **kwargs):
         variable_num = state_dict["backbone.g_a.patch_embed.proj.weight"].size(1)
         new_sd = OrderedDict()
         for k, v in state_dict.items():
             if 'kl_loss.logvar' not in k:
                 new_sd[k.replace("backbone.", "")] = v
-        net = cls(variable_num)
+        net = cls(variable_num, **kwargs)
         net.load_state_dict(new_sd)
         return net
 
@@ -490,20 +493,25 @@ class VAEformer(nn.Module):
             raise RuntimeError("cra5_amd.VAEformer computes only on an MI355X (HIP kernels, no CPU fallback). "
                                "Move the model with .to('cuda'); the CPU restatement lives in oracle/ (tests only).")
 
-    def _buf(self, name, shape, dtype=torch.float32, zero=False):
-        """Persistent workspace, allocated once per (thread, device): concurrent frame
-        pipelines (cra5_amd/pipeline.py: one host thread + one HIP stream per in-flight
-        frame) never share activation buffers; weights are shared read-only."""
-        ws = getattr(self._tls, "ws", None)
+    def _cached(self, kind, name, key, make):
+        """Persistent per-thread buffer `name` of one `kind` ("dev": device fp32 / bytes, "split": split matrices, "pin":
+        pinned host memory), rebuilt by `make()` when its `key` (shape, dtype, device) changes.  Concurrent frame
+        pipelines (cra5_amd/pipeline.py: one host thread + one HIP stream per in-flight frame) never share activation
+        buffers; weights are shared read-only.  The kinds are separate namespaces: a name such as `att{D}` exists as
+        "dev" (f32 engines) and as "split", and the range guard switches between the two on one thread."""
+        ws = getattr(self._tls, "bufs", None)
         if ws is None:
-            ws = self._tls.ws = {}
-        key = (name, tuple(shape), dtype, self.device)
+            ws = self._tls.bufs = {"dev": {}, "split": {}, "pin": {}}
+        ws = ws[kind]
         b = ws.get(name)
         if b is None or b[0] != key:
-            t = (torch.zeros if zero else torch.empty)(shape, device=self.device, dtype=dtype)
-            ws[name] = (key, t)
-            return t
+            b = ws[name] = (key, make())
         return b[1]
+
+    def _buf(self, name, shape, dtype=torch.float32, zero=False):
+        dev = self.device
+        return self._cached("dev", name, (tuple(shape), dtype, dev),
+                            lambda: (torch.zeros if zero else torch.empty)(shape, device=dev, dtype=dtype))
 
     def _derive(self, name, src, fn):
         """GEMM-ready re-layouts of weights, cached until the parameter changes."""
@@ -526,15 +534,8 @@ class VAEformer(nn.Module):
     # emit the split layout directly.  gemm_mode "f32": the exact v_mfma_f32_32x32x2_f32 kernel
     # (csrc/gemm_f32.hip) - kept as the bit-for-bit-fmaf reference engine.
     def _sbuf(self, name, rows, K, zero=False):
-        ws = getattr(self._tls, "sws", None)
-        if ws is None:
-            ws = self._tls.sws = {}
-        key = (rows, K, self.device)
-        b = ws.get(name)
-        if b is None or b[0] != key:
-            b = (key, ops.SplitMat.empty(rows, K, self.device, zero=zero))
-            ws[name] = b
-        return b[1]
+        dev = self.device
+        return self._cached("split", name, (rows, K, dev), lambda: ops.SplitMat.empty(rows, K, dev, zero=zero))
 
     def _weight2d(self, key, w):
         """GEMM-ready [N, K] view / re-layout of a parameter (cached)."""
@@ -840,49 +841,45 @@ class VAEformer(nn.Module):
         device->host hand-off to the entropy coder needs anyway).  When several frames are in
         flight (cra5_amd/pipeline.py) phases of different frames take turns on the GPU at this
         granularity while the other frames sit in their host rANS phase: every kernel runs
-        alone on the chip (clean per-kernel timing, no L2 thrash between frames)."""
+        alone on the chip (clean per-kernel timing, no L2 thrash between frames).  With gpu_exclusive off the phases
+        overlap: at most gpu_slots of them at a time (_SlotGate, `prio`), the `light` h_s phase ungated."""
         log = self.phase_log
         t0 = time.perf_counter() if log is not None else 0.0
-        if not self.gpu_exclusive:
-            sem = None
-            if self.gpu_slots > 0 and not light:
-                sem = self._gpu_sem
-                if sem is None or sem[0] != self.gpu_slots:
-                    with self._gpu_lock:
-                        sem = self._gpu_sem
-                        if sem is None or sem[0] != self.gpu_slots:
-                            sem = self._gpu_sem = (self.gpu_slots, _SlotGate(self.gpu_slots))
-                sem[1].acquire(prio)
+        exclusive = self.gpu_exclusive
+        gate = None                        # exclusive: the model's lock; shared: a slot (gpu_slots > 0) or nothing
+        if exclusive:
+            gate = self._gpu_lock
+            gate.acquire()
+        elif self.gpu_slots > 0 and not light:
+            n = self.gpu_slots
+            sem = self._gpu_sem
+            if sem is None or sem[0] != n:
+                with self._gpu_lock:
+                    sem = self._gpu_sem
+                    if sem is None or sem[0] != n:
+                        sem = self._gpu_sem = (n, _SlotGate(n))
+            gate = sem[1]
+            gate.acquire(prio)
+        try:
             t1 = time.perf_counter() if log is not None else 0.0
-            try:
-                if light:
-                    # the ~1 ms h_s phase sits between a frame's two host phases: on a high-priority
-                    # HIP stream its small kernels are scheduled ahead of the other frames' queued
-                    # blocks instead of behind them (the previous phase of this frame ended with a
-                    # stream sync, so switching streams needs no event)
-                    hp = getattr(self._tls, "hp_stream", None)
-                    if hp is None:
-                        hp = self._tls.hp_stream = torch.cuda.Stream(device=self.device, priority=-1)
-                    with torch.cuda.stream(hp), ops.stream_scope():
-                        yield
-                        hp.synchronize()
-                else:
-                    with ops.stream_scope():   # (the launch stream of this thread, looked up once per phase)
-                        yield
-                    torch.cuda.current_stream().synchronize()
-            finally:
-                if sem is not None:
-                    sem[1].release()
-            if log is not None:
-                log.append((threading.get_ident(), t0, t1, time.perf_counter()))
-            return
-        with self._gpu_lock:
-            t1 = time.perf_counter() if log is not None else 0.0
-            with ops.stream_scope():
+            stream = contextlib.nullcontext()
+            if light and not exclusive:
+                # the ~1 ms h_s phase sits between a frame's two host phases: on a high-priority
+                # HIP stream its small kernels are scheduled ahead of the other frames' queued
+                # blocks instead of behind them (the previous phase of this frame ended with a
+                # stream sync, so switching streams needs no event)
+                hp = getattr(self._tls, "hp_stream", None)
+                if hp is None:
+                    hp = self._tls.hp_stream = torch.cuda.Stream(device=self.device, priority=-1)
+                stream = torch.cuda.stream(hp)
+            with stream, ops.stream_scope():   # (the launch stream of this thread, looked up once per phase)
                 yield
-            torch.cuda.current_stream().synchronize()
+                torch.cuda.current_stream().synchronize()
             if log is not None:
                 log.append((threading.get_ident(), t0, t1, time.perf_counter()))
+        finally:
+            if gate is not None:
+                gate.release()
 
     def _scale_bound(self):
         """GaussianConditional.lower_bound_scale.bound as a host float, cached: reading a device
@@ -896,16 +893,7 @@ class VAEformer(nn.Module):
         return c[1]
 
     def _pinned(self, name, shape, dtype):
-        """Per-thread pinned host staging buffer."""
-        ws = getattr(self._tls, "pin", None)
-        if ws is None:
-            ws = self._tls.pin = {}
-        key = (tuple(shape), dtype)
-        b = ws.get(name)
-        if b is None or b[0] != key:
-            b = (key, torch.empty(shape, dtype=dtype, pin_memory=True))
-            ws[name] = b
-        return b[1]
+        return self._cached("pin", name, (tuple(shape), dtype), lambda: torch.empty(shape, dtype=dtype, pin_memory=True))
 
     def _pack(self, name, fields):
         """One per-thread device byte buffer holding several typed records back to back (16-byte aligned): the phase's
@@ -940,19 +928,22 @@ class VAEformer(nn.Module):
             return y, self._finite(flag), None
         return self._range_guard(0, run, "encode")
 
+    def _g_s_probed(self, y_hat, mean, std):
+        """g_s of one frame inside the caller's GPU phase -> (x_hat, pinned probe values: test them with _finite once
+        the phase has ended).  The residual stream after the last block carries every upstream poison - token-wise, and
+        the global attention spreads it.  The final LayerNorm's split store is O(gamma * sqrt(D)): a checkpoint with
+        |gamma| sqrt(D) >= 65 504, or a non-finite mean / std, poisons x_hat BEHIND that probe - a strided sample of the
+        reconstruction itself (every 2053rd pixel: ~14 samples of each token's 268 x 110-pixel patch, ~500 of every
+        channel) is probed as well."""
+        x_hat = self._decode_frame(y_hat, mean=mean, std=std)
+        D = self.cfg['embed_dim']
+        return x_hat, self._to_host("ok1", self._probe(self._buf(f"t{D}", (self.Hp * self.Wp, D)), (x_hat, 2053)))
+
     def _decode_guarded(self, y_hat, mean=None, std=None):
         """g_s of one frame under the range guard: y_hat [L, Hp, Wp] -> x_hat [C, H, W]."""
-        D = self.cfg['embed_dim']
-
         def run():
             with self._gpu_phase():
-                x_hat = self._decode_frame(y_hat, mean=mean, std=std)
-                # (the residual stream after the last block carries every upstream poison - token-wise, and the global
-                # attention spreads it.  The final LayerNorm's split store is O(gamma * sqrt(D)): a checkpoint with
-                # |gamma| sqrt(D) >= 65 504, or a non-finite mean / std, poisons x_hat BEHIND that probe - a strided
-                # sample of the reconstruction itself (every 2053rd pixel: ~14 samples of each token's 268 x 110-pixel
-                # patch, ~500 of every channel) is probed as well: ADVICE r4)
-                flag = self._to_host("ok1", self._probe(self._buf(f"t{D}", (self.Hp * self.Wp, D)), (x_hat, 2053)))
+                x_hat, flag = self._g_s_probed(y_hat, mean, std)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, run, "decode")
 
@@ -962,8 +953,7 @@ class VAEformer(nn.Module):
             s = self._latent_side_frame(y, want_lik=want_lik)
             flag = self._to_host("ok_h", self._probe(*self._hs_parent(s["scales"], s["means"])))
         if not self._finite(flag):
-            raise FloatingPointError("the hyper-prior path produced non-finite entropy parameters (pinned engine, no "
-                                     "fallback): the latent handed in is non-finite, or the checkpoint is broken")
+            raise self._hyper_nonfinite("latent side", "the latent handed in is non-finite, or the checkpoint is broken")
         return s
 
     @torch.no_grad()
@@ -1084,13 +1074,12 @@ class VAEformer(nn.Module):
             self.host_log.append(("enc", time.perf_counter() - t_host))
         return y_str, z_str
 
-    @torch.no_grad()
-    def compress_from_latent(self, y):
-        """vaeformer.py:334-348."""
+    def _compress_batch(self, frames):
+        """compress() / compress_from_latent(): `frames` yields one _compress_frame keyword dict per batch element."""
         self._require_gpu()
         ystr, zstr, nesc = [], [], []
-        for b in range(y.shape[0]):
-            a, c = self._compress_frame(y=y[b])
+        for kw in frames:
+            a, c = self._compress_frame(**kw)
             ystr.append(a)
             zstr.append(c)
             nesc.append(self._tls.last_n_escape)
@@ -1098,17 +1087,14 @@ class VAEformer(nn.Module):
         return {"strings": [ystr, zstr], "z_shape": torch.Size([self.Hz, self.Wz])}
 
     @torch.no_grad()
+    def compress_from_latent(self, y):
+        """vaeformer.py:334-348."""
+        return self._compress_batch(dict(y=y[b]) for b in range(y.shape[0]))
+
+    @torch.no_grad()
     def compress(self, x):
         """vaeformer.py:350-376."""
-        self._require_gpu()
-        ystr, zstr, nesc = [], [], []
-        for b in range(x.shape[0]):
-            a, c = self._compress_frame(x=x[b])
-            ystr.append(a)
-            zstr.append(c)
-            nesc.append(self._tls.last_n_escape)
-        self._tls.n_escape = nesc     # (not a dict key: the returned dict has exactly the reference's two)
-        return {"strings": [ystr, zstr], "z_shape": torch.Size([self.Hz, self.Wz])}
+        return self._compress_batch(dict(x=x[b]) for b in range(x.shape[0]))
 
     def last_n_escape(self):
         """Escape-coded symbols of each y stream the calling thread's last compress() / compress_from_latent() wrote
@@ -1171,9 +1157,8 @@ class VAEformer(nn.Module):
                 idx_h = self._to_host("idx", idx)
                 ok_h = self._to_host("ok_h", self._probe(*par))
         if not self._finite(ok_h):
-            raise FloatingPointError("decompress: the hyper-prior path produced non-finite entropy parameters (pinned "
-                                     "engine, no fallback): the stream does not belong to this checkpoint, or the "
-                                     "checkpoint is broken")
+            raise self._hyper_nonfinite("decompress", "the stream does not belong to this checkpoint, or the checkpoint "
+                                                      "is broken")
         y_host = None
         t_host = time.perf_counter()
         if compact:
@@ -1205,10 +1190,7 @@ class VAEformer(nn.Module):
                     y_hat = ops.gaussian_conditional(scales, means, gc.scale_table, sym_in=y_sym, want=("y_hat",))["y_hat"]
                 if not reconstruct:
                     return y_hat, True, None
-                x_hat = self._decode_frame(y_hat, mean=mean, std=std)
-                flag = self._to_host("ok1", self._probe(self._buf(f"t{self.cfg['embed_dim']}",
-                                                                  (self.Hp * self.Wp, self.cfg['embed_dim'])),
-                                                        (x_hat, 2053)))
+                x_hat, flag = self._g_s_probed(y_hat, mean, std)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, gpu_side, "decompress")
 

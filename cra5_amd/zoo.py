@@ -4,9 +4,9 @@ cra5/models/compressai/zoo/image.py:302-324 (+ `_load_model` :275-300, `load_pre
 
 Differences, stated: quality 159 is accepted (same architecture, 159 variables; the
 reference's zoo raises ValueError for anything but 268); `pretrained=True` cannot download
-(no network) - the checkpoint is read from `$CRA5_WEIGHTS` or
-`~/.cache/torch/hub/checkpoints/cra5_268v_300k.pth` if present, otherwise the reference's
-RuntimeError("Pre-trained model not yet available") is raised.
+(no network) - the checkpoint is read from `runtime=`'s `weights` (without an object:
+`$CRA5_WEIGHTS`) or `~/.cache/torch/hub/checkpoints/cra5_268v_300k.pth` if present, otherwise
+the reference's RuntimeError("Pre-trained model not yet available") is raised.
 """
 import os
 
@@ -50,13 +50,13 @@ def load_pretrained(state_dict):
     return {rename_key(k): v for k, v in state_dict.items()}
 
 
-def _find_checkpoint(architecture, quality):
-    """$CRA5_WEIGHTS / the hub cache hold VAEformer checkpoints only: the CNN architectures have no published
-    weights in the reference either (zoo/image.py:290 raises for them)."""
+def _find_checkpoint(architecture, quality, runtime=None):
+    """`runtime.weights` (without an object: $CRA5_WEIGHTS) / the hub cache hold VAEformer checkpoints only: the CNN
+    architectures have no published weights in the reference either (zoo/image.py:290 raises for them)."""
     if architecture != "vaeformer-pretrained":
         return None
     from .config import RuntimeConfig
-    cands = [RuntimeConfig.from_env().weights or None]       # CRA5_WEIGHTS (cra5_amd/config.py)
+    cands = [(runtime or RuntimeConfig.from_env()).weights or None]       # cra5_amd/config.py
     name = _CKPT_NAMES.get(quality)
     if name:
         cands.append(os.path.join(torch.hub.get_dir(), "checkpoints", name))
@@ -72,13 +72,13 @@ def _load_model(architecture, metric, quality, pretrained=False, progress=True, 
     if quality not in cfgs[architecture]:
         raise ValueError(f'Invalid quality value "{quality}"')
     if pretrained:
-        path = _find_checkpoint(architecture, quality) if metric == "mse" else None
+        path = _find_checkpoint(architecture, quality, kwargs.get("runtime")) if metric == "mse" else None
         if path is None:
             raise RuntimeError("Pre-trained model not yet available")
         state_dict = torch.load(path, map_location="cpu")
         if "state_dict" in state_dict:
             state_dict = state_dict["state_dict"]
-        return model_architectures[architecture].from_state_dict(load_pretrained(state_dict))
+        return model_architectures[architecture].from_state_dict(load_pretrained(state_dict), **kwargs)
     return model_architectures[architecture](*cfgs[architecture][quality], **kwargs)
 
 

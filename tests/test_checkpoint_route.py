@@ -31,9 +31,9 @@ class ThinVAEformer(VAEformer):
     full-spatial architecture (8 variables) under the zoo's "vaeformer-pretrained" key so that the WHOLE route runs in
     seconds; the 1.6 GB 268 checkpoint goes through the same code in the -m gpu test below."""
 
-    def __init__(self, variable_num):
+    def __init__(self, variable_num, **kwargs):
         assert variable_num == 8
-        super().__init__(0, **synth.thin_model_kwargs())
+        super().__init__(0, **synth.thin_model_kwargs(), **kwargs)
 
 
 def _source_model(cls=None):
@@ -97,6 +97,57 @@ def test_pretrained_route_loads_reference_layouts(source, ckpt_dir, layout, monk
     assert eb._quantized_cdf.dtype == torch.int32 and eb._quantized_cdf.numel() > 0
     assert not any("kl_loss" in k for k in net.state_dict())
     os.remove(path)
+
+
+def test_pretrained_route_takes_the_callers_runtime(source, ckpt_dir, monkeypatch):
+    """An explicit `runtime=` reaches the model on the pretrained route, through `vaeformer_pretrained` and through
+    `cra5_api`: its `weights` names the checkpoint (the environment's is not read) and the net holds its settings."""
+    from cra5_amd.api import cra5_api
+    from cra5_amd.config import RuntimeConfig
+    path = str(ckpt_dir / "cra5_268v_runtime.pth")
+    torch.save(_checkpoint_dict(source, "backbone"), path)
+    monkeypatch.setitem(zoo.model_architectures, "vaeformer-pretrained", ThinVAEformer)
+    cfg = RuntimeConfig(weights=path, precision="f16", gemm_engine="f32", gpu_slots=2, range_guard=False)
+    for env in (None, str(ckpt_dir / "elsewhere.pth")):
+        if env is None:
+            monkeypatch.delenv("CRA5_WEIGHTS", raising=False)
+        else:
+            monkeypatch.setenv("CRA5_WEIGHTS", env)
+        net = vaeformer_pretrained(quality=268, pretrained=True, runtime=cfg)
+        assert isinstance(net, ThinVAEformer) and net.runtime == cfg
+        assert (net.precision, net.gemm_mode, net.gpu_slots, net.range_guard) == ("f16", "f32", 2, False)
+        _assert_same_state(source, net)
+        api = cra5_api(device="cpu", runtime=cfg)
+        assert isinstance(api.net, ThinVAEformer) and api.runtime == cfg and api.net.runtime == cfg
+        _assert_same_state(source, api.net)
+    os.remove(path)
+
+
+def test_settings_are_properties_over_the_runtime_object():
+    """Assigning a setting of a model / API replaces its `runtime` with a copy that RuntimeConfig validated; the
+    caller's object is never changed."""
+    from cra5_amd.api import cra5_api
+    from cra5_amd.config import RuntimeConfig
+    cfg = RuntimeConfig()
+    net = ThinVAEformer(8, runtime=cfg)
+    assert net.runtime is cfg
+    net.precision = "f16"
+    assert net.precision == "f16" and net.runtime.precision == "f16" and cfg.precision == "fp32"
+    net.gemm_mode, net.attn_mode, net.range_guard, net.gpu_exclusive, net.gpu_slots = "f32", "f32", False, False, 5
+    assert net.runtime == cfg.replace(precision="f16", gemm_engine="f32", attn_engine="f32", range_guard=False,
+                                      gpu_exclusive=False, gpu_slots=5)
+    assert (net.gemm_mode, net.attn_mode, net.range_guard, net.gpu_exclusive, net.gpu_slots) == ("f32", "f32", False, False, 5)
+    for name, bad in (("precision", "bf16"), ("attn_mode", "x"), ("gemm_mode", "blas"), ("gpu_slots", -1)):
+        with pytest.raises(ValueError):
+            setattr(net, name, bad)
+    assert net.runtime.precision == "f16" and net.attn_mode == "f32" and cfg == RuntimeConfig()
+    api = cra5_api(device="cpu", weights=net)
+    assert api.runtime is net.runtime
+    api.link_serial, api.batch_copy_threads = False, 4
+    assert (api.runtime.link_serial, api.runtime.batch_copy_threads) == (False, 4) and net.runtime.link_serial is True
+    with pytest.raises(ValueError):
+        api.batch_copy_threads = 0
+    assert api.batch_copy_threads == 4
 
 
 _DEFAULT_W = []
