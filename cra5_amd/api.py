@@ -28,27 +28,58 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import binfmt, ops
+from . import binfmt, ops, subset
 from .config import RuntimeConfig, runtime_setting
 from .zoo import vaeformer_pretrained
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
+def _variables_of(config=None):
+    """(ERA5 statistics, vnames, total_levels, pressure_level) of the default 268-variable set, or of a reference-style
+    python config file that overrides `vnames` / `pressure_level` (cra5_268v_config.py:48-54)."""
+    with open(os.path.join(_HERE, "data", "era5_stats.json")) as f:
+        stats = json.load(f)
+    vnames = dict(pressure=list(stats["pressure"]), single=list(stats["single"]))
+    total_levels = list(stats["total_levels"])
+    pressure_level = list(total_levels)
+    if config is not None:
+        ns = {}
+        exec(compile(open(config).read(), config, "exec"), ns)  # noqa: S102 (user-supplied config file)
+        vnames = ns.get("vnames", vnames)
+        pressure_level = ns.get("pressure_level", pressure_level)
+    return stats, vnames, total_levels, pressure_level
+
+
+def _channel_mapping(vnames, pressure_level):
+    """cra5_api.py:228-241: pressure variables x levels, then the single-level variables."""
+    c2v, v2c = {}, {}
+    ch = 0
+    for v in vnames['pressure']:
+        for level in pressure_level:
+            c2v[ch] = v + '_' + str(int(level))
+            v2c[v + '_' + str(int(level))] = ch
+            ch += 1
+    for v in vnames['single']:
+        c2v[ch] = v
+        v2c[v] = ch
+        ch += 1
+    return c2v, v2c
+
+
+def variable_mapping(config=None):
+    """(channels_to_vname, vname_to_channels) of the default 268-variable set or of a config file (e.g. a 159-variable
+    one) - what cra5_api(config=...).channel_vname_mapping() returns, without a model or a GPU."""
+    _, vnames, _, pressure_level = _variables_of(config)
+    return _channel_mapping(vnames, pressure_level)
+
+
 class cra5_api:
     def __init__(self, config=None, local_root=None, device=None, ceph_cfg=None, weights=None, quality=268, runtime=None):
         self.device = device or ('cuda' if torch.cuda.is_available() else 'cpu')
         print(f'The serving device is {self.device}')
-        with open(os.path.join(_HERE, "data", "era5_stats.json")) as f:
-            self._stats = json.load(f)
-        self.vnames = dict(pressure=list(self._stats["pressure"]), single=list(self._stats["single"]))
-        self.total_levels = list(self._stats["total_levels"])
-        self.pressure_level = list(self.total_levels)  # cra5_268v_config.py:48-54
-        if config is not None:  # a reference-style python config may override vnames / levels
-            ns = {}
-            exec(compile(open(config).read(), config, "exec"), ns)  # noqa: S102 (user-supplied config file)
-            self.vnames = ns.get("vnames", self.vnames)
-            self.pressure_level = ns.get("pressure_level", self.pressure_level)
+        # (a reference-style python config may override vnames / levels)
+        self._stats, self.vnames, self.total_levels, self.pressure_level = _variables_of(config)
         self.level_mapping = [self.total_levels.index(v) for v in self.pressure_level if v in self.total_levels]
         mean, std = self.get_mean_std()
         self.mean = torch.from_numpy(mean[:, np.newaxis, np.newaxis]).to(self.device)
@@ -164,18 +195,26 @@ class cra5_api:
 
     def channel_vname_mapping(self):
         """cra5_api.py:228-241."""
-        c2v, v2c = {}, {}
-        ch = 0
-        for v in self.vnames['pressure']:
-            for level in self.pressure_level:
-                c2v[ch] = v + '_' + str(int(level))
-                v2c[v + '_' + str(int(level))] = ch
-                ch += 1
-        for v in self.vnames['single']:
-            c2v[ch] = v
-            v2c[v] = ch
-            ch += 1
-        return c2v, v2c
+        return _channel_mapping(self.vnames, self.pressure_level)
+
+    # ------------------------------------------------------------------ subsets (decode_from_bin / decode_batch)
+    # variables=[names] and / or region=(lat_min, lat_max, lon_min, lon_max) in degrees: the decode returns those channels
+    # (in the order given) over that box - the same values as the slice of a full decode, bit for bit - and only the
+    # subset is written on the GPU, crosses the host link and lands in host memory (DESIGN.md, "Subset decode").
+    grid_box = staticmethod(subset.grid_box)
+    resolve_variables = staticmethod(subset.resolve_variables)
+
+    def _subset(self, variables, region):
+        """-> (channel indices | None, grid box | None, the result dict's extra keys) for the model; (None, None, None)
+        without a subset."""
+        if variables is None and region is None:
+            return None, None, None
+        H, W = self.net.cfg['img_size']
+        chans = subset.resolve_variables(variables, self.vname_to_channels)
+        g = subset.grid_box(region if region is not None else (-90.0, 90.0, 0.0, 360.0), H, W)
+        names = [self.channels_to_vname.get(c, str(c)) for c in (chans if chans is not None else range(self.net.cfg['out_chans']))]
+        channels, box = self.net._subset_args(chans, g["box"] if region is not None else None)
+        return channels, box, dict(variables=names, lat=g["lat"], lon=g["lon"])
 
     def get_mean_std(self):
         """cra5_api.py:243-261."""
@@ -438,18 +477,17 @@ class cra5_api:
         return self._pipeline(workers).map(lambda it: self._encode_one(it[0], it[1], save_root, write),
                                            list(zip(time_stamps, frames)))
 
-    def _decode_one(self, i, path, denorm, out=None, sink=None):
-        """One frame of the batch decode on the calling frame thread: .bin -> x_hat -> this thread's pinned buffer ->
-        `sink` / `out[i]` / a fresh array."""
-        C = self.net.cfg['out_chans']
-        H, W = self.net.cfg['img_size']
+    def _decode_one(self, i, path, denorm, out=None, sink=None, channels=None, box=None):
+        """One frame of the batch decode on the calling frame thread: .bin -> x_hat (or its subset: canonical channels /
+        box of VAEformer._subset_args) -> this thread's pinned buffer -> `sink` / `out[i]` / a fresh array."""
         lstrings, shape = self._read_bin(path)
         with torch.no_grad():
             t_d = time.perf_counter()
             x_hat = self.net._decompress_frame(lstrings[0][0], lstrings[1][0], shape, True,
                                                mean=self._mean_flat if denorm else None,
-                                               std=self._std_flat if denorm else None)
+                                               std=self._std_flat if denorm else None, channels=channels, box=box)
             self._log("decompress", t_d)
+            C, H, W = x_hat.shape[-3:]
             pin = self.net._pinned("api_x_out", (C, H, W), torch.float32)
             if sink is None and out is not None and self.batch_copy_threads > 1:
                 with self._link("d2h"):
@@ -469,13 +507,16 @@ class cra5_api:
         finally:
             self._log("consume", t_s)
 
-    def _check_out(self, out, n):
-        """`out=` of the batch methods: the C memcpy / DMA behind it writes n x C x H x W float32 values, so anything else
-        is refused here with a ValueError (not an assert that `python -O` drops - ADVICE r5)."""
+    def _check_out(self, out, n, frame_shape=None):
+        """`out=` of the batch methods: the C memcpy / DMA behind it writes n x C x H x W float32 values (`frame_shape`
+        = (C, H, W): a subset's), so anything else is refused here with a ValueError (not an assert that `python -O`
+        drops - ADVICE r5)."""
         if out is None:
             return
         C = self.net.cfg['out_chans']
         H, W = self.net.cfg['img_size']
+        if frame_shape is not None:
+            C, H, W = frame_shape
         if not isinstance(out, np.ndarray) or out.dtype != np.float32 or tuple(out.shape) != (n, C, H, W) \
                 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
             raise ValueError(f"`out` must be a writeable C-contiguous float32 numpy array of shape [{n}, {C}, {H}, {W}]"
@@ -501,24 +542,29 @@ class cra5_api:
             return enc, self._decode_one(i, enc["save_path"], denorm, out, sink)
         return self._pipeline(workers).map(one, [(i, ts, a) for i, (ts, a) in enumerate(zip(time_stamps, frames))])
 
-    def decode_batch(self, time_stamps=None, paths=None, return_format='de_normalized', out=None, workers=12, sink=None):
+    def decode_batch(self, time_stamps=None, paths=None, return_format='de_normalized', out=None, workers=12, sink=None,
+                     variables=None, region=None):
         """decode_from_bin for many frames.  Returns a list of HOST float32 arrays [C, H, W] (views of `out`
         [n, C, H, W] when given, fresh arrays otherwise); the D2H of each reconstruction goes through the
         decoding thread's pinned buffer and overlaps the other frames' work.  `sink(i, frame)`: called on the decoding
         thread with frame i as a [C, H, W] float32 view of that thread's PINNED buffer (valid until the call returns:
         write it to disk, reduce it, copy it) instead of copying it out; the list then holds the sink's return values -
-        a long decode loop needs no [n, C, H, W] host array."""
+        a long decode loop needs no [n, C, H, W] host array.
+        variables / region (decode_from_bin): every frame is the subset [C', Hb, Wb] - `out` must then be
+        [n, C', Hb, Wb], `sink` gets [C', Hb, Wb] views; grid_box(region) gives its lat / lon."""
         if paths is None:
             paths = [f'{self.local_root}/CRA5/{ts[:4]}/{ts}.bin' for ts in time_stamps]
         if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
             raise ValueError(f"unknown return_format {return_format!r}")
         denorm = return_format != 'normalized'
         self.net._require_gpu()
-        C = self.net.cfg['out_chans']
-        H, W = self.net.cfg['img_size']
-        self._check_out(out, len(paths))
+        channels, box, meta = self._subset(variables, region)
+        shape = None
+        if meta is not None:
+            shape = (len(meta["variables"]), len(meta["lat"]), len(meta["lon"]))
+        self._check_out(out, len(paths), shape)
 
-        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink),
+        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box),
                                            list(enumerate(paths)))
 
     def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights):
@@ -595,14 +641,26 @@ class cra5_api:
         with torch.no_grad():
             return self.net.decompress(lstrings, shape, return_format='latent')
 
-    def latent_to_reconstruction(self, y_hat):
-        """cra5_api.py:146-151 (normalised units)."""
+    def latent_to_reconstruction(self, y_hat, variables=None, region=None):
+        """cra5_api.py:146-151 (normalised units).  variables / region: that subset (decode_from_bin)."""
+        channels, box, _ = self._subset(variables, region)
         with torch.no_grad():
-            return self.net.decode_latent(y_hat)
+            return self.net.decode_latent(y_hat, channels=channels, box=box)
 
-    def decode_from_bin(self, time_stamp=None, custom_path=None, return_format='de_normalized', to_host=False, out=None):
+    def decode_from_bin(self, time_stamp=None, custom_path=None, return_format='de_normalized', to_host=False, out=None,
+                        variables=None, region=None):
         """cra5_api.py:153-192.  `to_host=True` (or `out=` a float32 array of the frame's shape): `x_hat` comes back
-        as a HOST numpy array through the pinned staging buffer instead of a device tensor."""
+        as a HOST numpy array through the pinned staging buffer instead of a device tensor.
+        variables: names of channel_vname_mapping() (e.g. ["z_500", "t_850", "t2m"]), output channels in that order;
+        region: (lat_min, lat_max, lon_min, lon_max) in degrees (grid_box).  Either gives x_hat [C', Hb, Wb] - the slice
+        of the full decode, bit for bit - and the dict then also carries `variables`, `lat` and `lon` (float64, lon in
+        [0, 360))."""
+        if return_format == 'latent' and (variables is not None or region is not None):
+            raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region select a "
+                             "subset of the reconstruction")
+        if return_format not in ('latent', 'normalized', 'de_normalized', 'de_normlized'):
+            raise ValueError(f"unknown return_format {return_format!r}")
+        channels, box, meta = self._subset(variables, region)
         bin_path = custom_path or f'{self.local_root}/CRA5/{time_stamp[:4]}/{time_stamp}.bin'
         decoding_start = time.time()
         lstrings, shape = self._read_bin(bin_path)
@@ -611,12 +669,11 @@ class cra5_api:
             if return_format == 'latent':
                 return y_hat
             if return_format == 'normalized':
-                x_hat = self.net.decode_latent(y_hat)
-            elif return_format in ('de_normalized', 'de_normlized'):
-                # fused de-normalisation in the overlap-add store
-                x_hat = self.net._decode_guarded(y_hat[0], mean=self._mean_flat, std=self._std_flat)
+                x_hat = self.net.decode_latent(y_hat, channels=channels, box=box)
             else:
-                raise ValueError(f"unknown return_format {return_format!r}")
+                # fused de-normalisation in the overlap-add store
+                x_hat = self.net._decode_guarded(y_hat[0], mean=self._mean_flat, std=self._std_flat, channels=channels,
+                                                 box=box)
             if to_host or out is not None:
                 src = x_hat.reshape(x_hat.shape[-3:]).contiguous()
                 if out is None:
@@ -626,4 +683,7 @@ class cra5_api:
                 pin = self.net._pinned("api_x_out", tuple(src.shape), torch.float32)
                 x_hat = ops.copy_d2h_staged(out, src, pin, threads=self.runtime.copy_threads)
         torch.cuda.synchronize()
-        return dict(x_hat=x_hat, decoding_time=time.time() - decoding_start)
+        res = dict(x_hat=x_hat, decoding_time=time.time() - decoding_start)
+        if meta is not None:
+            res.update(meta)
+        return res

@@ -580,13 +580,17 @@ static int gemm_dispatch(const unsigned short *A, long lda, const unsigned short
   constexpr int forced = 0;
 #endif
   const bool longk = Kp > 8192;
+  // CRA5_GEMM_WIDE_K: the wide reduced-precision form at any size (a slice of a big launch, same summation order)
+  const bool force_wide = flags & CRA5_GEMM_WIDE_K;
+  if (force_wide && (!(flags & CRA5_GEMM_HI_ONLY) || longk || (Kp % 64))) return CRA5_ERR_ARG;
   // plain-f16 operands / output exist in the wide reduced-precision form only (the caller falls back to split rows)
   constexpr int PLAIN_ANY = CRA5_GEMM_A_PLAIN | CRA5_GEMM_W_PLAIN | CRA5_GEMM_OUT_PLAIN;
-  if ((flags & PLAIN_ANY) && (!(flags & CRA5_GEMM_HI_ONLY) || longk || tiles128 < 256 || (Kp % 64))) return CRA5_ERR_ARG;
+  if ((flags & PLAIN_ANY) && (!(flags & CRA5_GEMM_HI_ONLY) || longk || (tiles128 < 256 && !force_wide) || (Kp % 64)))
+    return CRA5_ERR_ARG;
   if (longk) CRA5_GO(2, 2, 2, 2, true);
   if (flags & CRA5_GEMM_HI_ONLY) {   // reduced precision: one f16 MFMA per product
     const bool wide = (M >= 1024 && N >= 2048);
-    if (tiles128 < 256)
+    if (tiles128 < 256 && !force_wide)
       return launch<2, 2, 1, 1, false, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
     if (Kp % 64 == 0) {   // wide form: 64 k-values (the hi halves of two chunks) per k-step, the fp32-accurate mode's loop
       if (wide)

@@ -296,7 +296,7 @@ def split_f16(x, scale_pow2=None, out=None):
     return out
 
 
-GEMM_A_PLAIN, GEMM_W_PLAIN, GEMM_OUT_PLAIN = 16, 32, 64
+GEMM_A_PLAIN, GEMM_W_PLAIN, GEMM_OUT_PLAIN, GEMM_WIDE_K = 16, 32, 64, 128
 
 
 def plain_ok(M, N, Kp):
@@ -306,10 +306,11 @@ def plain_ok(M, N, Kp):
 
 
 def gemm_nt_split(a, w, bias=None, res=None, gelu=False, out=None, out_split=None, want_f32=True, hi_only=False,
-                  out_plain=False):
+                  out_plain=False, wide_k=False):
     """epi(a @ w^T) with a, w SplitMat (same K).  out: fp32 [M, N] (row-strided ok) unless
     want_f32=False; out_split: SplitMat [M, N] to receive the split-f16 result.  Reduced-precision mode (hi_only): a / w
-    may be PLAIN matrices (SplitMat.plain) and out_plain=True writes out_split's rows plain."""
+    may be PLAIN matrices (SplitMat.plain) and out_plain=True writes out_split's rows plain; wide_k=True takes the
+    64-wide k-step form (CRA5_GEMM_WIDE_K) at any size - the summation order of the big launches this one is a slice of."""
     _devs(a.data, w.data)
     _dev(bias, res, out)
     M, N = a.rows, w.rows
@@ -325,6 +326,9 @@ def gemm_nt_split(a, w, bias=None, res=None, gelu=False, out=None, out_split=Non
     if a.plain or w.plain or out_plain:
         assert hi_only, "plain-f16 operands exist in the reduced-precision mode only"
         flags |= (GEMM_A_PLAIN if a.plain else 0) | (GEMM_W_PLAIN if w.plain else 0) | (GEMM_OUT_PLAIN if out_plain else 0)
+    if wide_k:
+        assert hi_only, "the 64-wide k-step form exists in the reduced-precision mode only"
+        flags |= GEMM_WIDE_K
     if out_split is not None:
         out_split.plain = bool(out_plain)
     ev = TIMER.start() if TIMER is not None else None
@@ -576,6 +580,48 @@ def col2im(cols, C, kh, kw, sh, sw, Hp, Wp, mean=None, std=None, out=None):
                                 _row_stride(cols), _stream()), "cra5_col2im_f32")
     if ev is not None:   # bytes: the column matrix read once + the frame written once
         TIMER.stop("col2im", ev, 4.0 * Hp * Wp * C * kh * kw + 4.0 * C * H * W)
+    return out
+
+
+def gather_token_rows(src, out, Hp, Wp, ti0, n_ti, tj0, n_tj):
+    """cra5_gather_token_rows: rows (ti0 + i) * Wp + (tj0 + j) mod Wp (i < n_ti, j < n_tj) of the token-major matrix `src`
+    (Hp * Wp rows) -> rows i * n_tj + j of `out`, verbatim.  src / out: both SplitMat (split or plain rows; `out` takes
+    src's layout) or both 2-D fp32 device tensors with unit inner stride."""
+    if isinstance(src, SplitMat):
+        if not isinstance(out, SplitMat) or out.Kp != src.Kp or out.K != src.K or out.rows != n_ti * n_tj:
+            raise ValueError("gather_token_rows: `out` must be a SplitMat of n_ti * n_tj rows and src's K")
+        _devs(src.data, out.data)
+        row_bytes = 2 * src.Kp if src.plain else 4 * src.Kp       # a plain row holds Kp halves, a split row 2 * Kp
+        s_t, d_t = src.data, out.data
+        out.scale_inv, out.plain = src.scale_inv, src.plain
+    else:
+        _dev(src, out)
+        if out.dim() != 2 or src.dim() != 2 or out.shape[1] != src.shape[1] or out.shape[0] != n_ti * n_tj \
+                or src.dtype != out.dtype:
+            raise ValueError("gather_token_rows: `out` must be [n_ti * n_tj, K] of src's K and dtype")
+        row_bytes = src.shape[1] * src.element_size()
+        s_t, d_t = src, out
+    if s_t.shape[0] != Hp * Wp:
+        raise ValueError(f"gather_token_rows: src has {s_t.shape[0]} rows, the grid {Hp} x {Wp} tokens")
+    es = s_t.element_size()
+    check(lib().cra5_gather_token_rows(_p(s_t), _row_stride(s_t) * es, _p(d_t), _row_stride(d_t) * es, row_bytes, Hp, Wp,
+                                       ti0, n_ti, tj0, n_tj, _stream()), "cra5_gather_token_rows")
+    return out
+
+
+def crop(src, r0, Hb, c0, Wb, out=None):
+    """cra5_crop_f32: out[c][i][j] = src[c][r0 + i][(c0 + j) mod Ws] - the box [C, Hb, Wb] of the contiguous image
+    src [C, Hs, Ws], columns wrapping at its east edge."""
+    _dev(src, out)
+    C, Hs, Ws = src.shape
+    if out is None:
+        out = torch.empty((C, Hb, Wb), device=src.device, dtype=torch.float32)
+    if not (src.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (C, Hb, Wb)):
+        raise ValueError(f"crop: src must be contiguous and out a contiguous [{C}, {Hb}, {Wb}] tensor")
+    ev = TIMER.start() if TIMER is not None else None
+    check(lib().cra5_crop_f32(_p(src), C, Hs, Ws, _p(out), r0, Hb, c0, Wb, _stream()), "cra5_crop_f32")
+    if ev is not None:
+        TIMER.stop("crop", ev, 8.0 * C * Hb * Wb)
     return out
 
 

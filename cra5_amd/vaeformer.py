@@ -27,7 +27,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, subset
 from ._lib import ERR_RANGE, Cra5Error, StreamDesyncError
 from .config import RuntimeConfig, runtime_setting
 from .entropy import EntropyBottleneck, GaussianConditional, get_scale_table
@@ -254,6 +254,8 @@ class _SlotGate:
 
 
 class VAEformer(nn.Module):
+    SUBSET_CACHE = 8
+
     def __init__(self, model_version, embed_dim=None, z_channels=None, y_channels=None, sample_posterior=None,
                  pretrained_vae=None, frozen_encoder=None, ddconfig=None, priorconfig=None,
                  rate_distortion_loss=None, kl_loss=None, ignore_keys=(), lower_dim=False, **kwargs):
@@ -313,6 +315,9 @@ class VAEformer(nn.Module):
         # results); "split" keeps the hi planes of split rows (rounds 1-4; a test flips the attribute)
         self.f16_layout = "plain"
         self._derived = {}
+        # subset decode: un-embed weight rows / mean / std of chosen channel tuples, least recently used first, at most
+        # SUBSET_CACHE entries (a long run over many different subsets does not grow device memory)
+        self._sub_cache = OrderedDict()
         self._derive_lock = threading.RLock()
         self._gpu_lock = threading.Lock()
         self._fallback_lock = threading.Lock()     # range-guard re-runs on the exact-f32 engines: one frame at a time
@@ -460,6 +465,7 @@ class VAEformer(nn.Module):
                     if buf.numel() == 0:
                         buf.resize_(state_dict[key].size())
         self._derived.clear()
+        self._sub_cache.clear()
         return nn.Module.load_state_dict(self, state_dict, strict=strict)
 
     def update(self, scale_table=None, force=False):
@@ -781,8 +787,9 @@ class VAEformer(nn.Module):
         return params[:L], params[L:]
 
     # ---- g_s --------------------------------------------------------------------------------
-    def _decode_frame(self, y_hat, mean=None, std=None):
-        """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300)."""
+    def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None):
+        """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300).  channels / box (canonical, _subset_args): the
+        [len(channels), r1 - r0, nc] slice of that frame, bit for bit (_unembed_subset)."""
         cfg = self.cfg
         D, L = cfg['embed_dim'], cfg['latent_dim']
         N = self.Hp * self.Wp
@@ -800,6 +807,8 @@ class VAEformer(nn.Module):
         p_ue = (self.precision == "f16" and self.f16_layout == "plain" and self.gemm_mode == "split" and D % 64 == 0
                 and self.fused_unembed and D <= 8192 and ops.unembed_side_bytes(Cout, Himg, Wimg, kh, kw, sh, sw) > 0)
         h = self._ln(t, self.g_s.norm, f"h{D}", plain=p_ue)
+        if channels is not None or box is not None:
+            return self._unembed_subset(h, mean, std, channels, box)
         x_hat = torch.empty((Cout, Himg, Wimg), device=self.device, dtype=torch.float32)
         nside = ops.unembed_side_bytes(Cout, Himg, Wimg, kh, kw, sh, sw) if self.gemm_mode == "split" else 0
         if nside and self.fused_unembed and D <= 8192:
@@ -815,6 +824,127 @@ class VAEformer(nn.Module):
         self._mm(h, "g_s.final", self.g_s.final.weight, out=cols)
         ops.col2im(cols, Cout, kh, kw, sh, sw, self.Hp, self.Wp, mean=mean, std=std, out=x_hat)
         return x_hat
+
+    # ---- subset decode: chosen channels and / or a lat-lon box of the reconstruction ------------------------
+    # The transformer runs on the whole grid (global attention); everything after the final LayerNorm is local.  The
+    # un-embed runs on the patch-aligned superset of tokens whose patches reach the box (subset.token_plan) with the
+    # chosen channels' weight rows, and a crop cuts the box out of the superset image: the same kernels on the same
+    # operand rows as the full decode - the box is the full decode's slice, bit for bit ("Subset decode").
+    def _subset_args(self, channels=None, box=None):
+        """Validate channel indices / a grid box (r0, r1, c0, nc) -> (tuple | None, tuple | None); None = every channel
+        in order / the whole grid (the full decode's path, unchanged)."""
+        C = self.cfg['out_chans']
+        H, W = self.cfg['img_size']
+        if channels is not None:
+            if isinstance(channels, (str, bytes)) or not hasattr(channels, "__iter__"):
+                raise ValueError(f"channels must be a list of channel indices, got {channels!r}")
+            ch = tuple(int(c) for c in channels)
+            if not ch:
+                raise ValueError("channels: the list is empty - pass None for every channel")
+            bad = [c for c in ch if not 0 <= c < C]
+            if bad:
+                raise ValueError(f"channels: indices {bad} outside [0, {C})")
+            if len(set(ch)) != len(ch):
+                raise ValueError(f"channels: an index is given more than once: {list(ch)}")
+            channels = None if ch == tuple(range(C)) else ch
+        if box is not None:
+            kh, kw = self.cfg['patch_size']
+            sh, sw = self.cfg['patch_stride']
+            subset.token_plan(box, H, W, kh, kw, sh, sw)      # (raises ValueError for a bad box / geometry)
+            box = tuple(int(v) for v in box)
+            if box == (0, H, 0, W):
+                box = None
+        return channels, box
+
+    def _sub_cached(self, key, src, make):
+        """Entry `key` of the bounded subset cache, rebuilt by `make()` when `src` (the tensor / derived weight it was
+        made from) is no longer the one it holds."""
+        with self._derive_lock:
+            e = self._sub_cache.get(key)
+            if e is not None and e[0] is src:
+                self._sub_cache.move_to_end(key)
+                return e[1]
+            with torch.no_grad():
+                v = make()
+            torch.cuda.current_stream().synchronize()   # visible to every stream
+            self._sub_cache[key] = (src, v)
+            while len(self._sub_cache) > self.SUBSET_CACHE:
+                self._sub_cache.popitem(last=False)
+            return v
+
+    def _rows_of_channels(self, kind, src, chans):
+        """The chosen channels' rows (c * kh * kw .. + kh * kw - 1 each, in the order given) of a cached un-embed weight
+        copy `src` (SplitMat: split or plain rows; fp32 tensor).  Gathered from the whole weight's copy, never re-split:
+        the split copy's power-of-two scale is the whole weight's, a sub-weight could get another one (other hi / lo)."""
+        kh, kw = self.cfg['patch_size']
+        n = kh * kw
+
+        def make():
+            idx = torch.tensor([c * n + k for c in chans for k in range(n)], device=self.device, dtype=torch.long)
+            if isinstance(src, ops.SplitMat):
+                return ops.SplitMat(src.data.index_select(0, idx), len(idx), src.K, src.Kp, src.scale_inv, plain=src.plain)
+            return src.index_select(0, idx)
+        return self._sub_cached(("w", kind, chans), src, make)
+
+    def _stats_of_channels(self, t, chans):
+        """mean / std [C] device vector -> its chosen entries (cached; None stays None)."""
+        if t is None or chans is None:
+            return t
+        return self._sub_cached(("stat", t.data_ptr(), t._version, chans), t,
+                                lambda: t.index_select(0, torch.tensor(chans, device=t.device, dtype=torch.long)))
+
+    def _unembed_subset(self, h, mean, std, chans, box):
+        """The un-embed of decode_frame for channels `chans` (tuple | None) inside grid box `box` (tuple | None), from
+        the final LayerNorm's output h (SplitMat, or fp32 [N, D] on the exact-f32 engines) -> a fresh [C', Hb, Wb]."""
+        cfg = self.cfg
+        D = cfg['embed_dim']
+        kh, kw = cfg['patch_size']
+        sh, sw = cfg['patch_stride']
+        Cout, (Himg, Wimg) = cfg['out_chans'], cfg['img_size']
+        p = subset.token_plan(box if box is not None else (0, Himg, 0, Wimg), Himg, Wimg, kh, kw, sh, sw)
+        Cs = len(chans) if chans is not None else Cout
+        ms, ss = self._stats_of_channels(mean, chans), self._stats_of_channels(std, chans)
+        split = self.gemm_mode == "split"
+        # A operand: the superset's token rows, verbatim.  A latitude band over the whole circle is a run of rows.
+        M, Hp, Wp = p["n_ti"] * p["n_tj"], self.Hp, self.Wp
+        if p["n_tj"] == Wp:
+            r = slice(p["ti0"] * Wp, p["ti0"] * Wp + M)
+            a = ops.SplitMat(h.data[r], M, h.K, h.Kp, h.scale_inv, plain=h.plain) if split else h[r]
+        else:
+            dst = self._sbuf("ue_a_sub", M, D) if split else self._buf("ue_a_sub", (M, D))
+            a = ops.gather_token_rows(h, dst, Hp, Wp, p["ti0"], p["n_ti"], p["tj0"], p["n_tj"])
+        Hs, Ws = p["Hs"], p["Ws"]
+        out = torch.empty((Cs, p["Hb"], p["Wb"]), device=self.device, dtype=torch.float32)
+        sup = out if p["exact"] else self._buf("ue_sup", (Cs, Hs, Ws))
+        key, w = "g_s.final", self.g_s.final.weight
+        nside = ops.unembed_side_bytes(Cs, Hs, Ws, kh, kw, sh, sw) if split else 0
+        if nside and self.fused_unembed and D <= 8192:
+            # the full decode's fused launch pair, unchanged, on the superset geometry (H = 10 n_ti + 1, W = 10 n_tj)
+            side = self._buf("ue_side_sub", (nside // 4,))
+            wfull = self._wplain(key, w) if h.plain else self._wsplit(key, w)
+            wue = wfull if chans is None else self._rows_of_channels("plain" if h.plain else "split", wfull, chans)
+            ops.gemm_unembed(a, wue, Cs, Hs, Ws, kh, kw, sh, sw, side, mean=ms, std=ss, out=sup,
+                             hi_only=self.precision == "f16")
+        else:
+            cols = self._buf("ue_cols_sub", (M, Cs * kh * kw))
+            if split:
+                # the full decode's GEMM (_mm) is ONE launch of M = Hp * Wp tokens x N = C * kh * kw columns: the weight
+                # copy it reads and its summation order are those of that shape, whatever the subset's size
+                Mf, Nf = Hp * Wp, Cout * kh * kw
+                wsp = self._wsplit(key, w)
+                hi = self.precision == "f16"
+                kind = "plain" if self._plain_gemm(key, Mf, Nf, wsp.K) else "split"
+                wfull = self._wplain(key, w) if kind == "plain" else wsp
+                wg = wfull if chans is None else self._rows_of_channels(kind, wfull, chans)
+                ops.gemm_nt_split(a, wg, out=cols, hi_only=hi, wide_k=hi and ops.plain_ok(Mf, Nf, wsp.Kp))
+            else:
+                wf = self._wf32(key, w)
+                wg = wf if chans is None else self._rows_of_channels("f32", wf, chans)
+                ops.gemm_nt(a, wg, out=cols)
+            ops.col2im(cols, Cs, kh, kw, sh, sw, p["n_ti"], p["n_tj"], mean=ms, std=ss, out=sup)
+        if not p["exact"]:
+            ops.crop(sup, p["r_off"], p["Hb"], p["c_off"], p["Wb"], out=out)
+        return out
 
     # ---- latent side: everything between y and the entropy coder ---------------------------
     def _latent_side_frame(self, y, want_lik=False, z_sym_out=None):
@@ -928,22 +1058,25 @@ class VAEformer(nn.Module):
             return y, self._finite(flag), None
         return self._range_guard(0, run, "encode")
 
-    def _g_s_probed(self, y_hat, mean, std):
+    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None):
         """g_s of one frame inside the caller's GPU phase -> (x_hat, pinned probe values: test them with _finite once
         the phase has ended).  The residual stream after the last block carries every upstream poison - token-wise, and
         the global attention spreads it.  The final LayerNorm's split store is O(gamma * sqrt(D)): a checkpoint with
         |gamma| sqrt(D) >= 65 504, or a non-finite mean / std, poisons x_hat BEHIND that probe - a strided sample of the
         reconstruction itself (every 2053rd pixel: ~14 samples of each token's 268 x 110-pixel patch, ~500 of every
-        channel) is probed as well."""
-        x_hat = self._decode_frame(y_hat, mean=mean, std=std)
+        channel) is probed as well.  A subset decode (channels / box) probes the decoded subset itself: every
+        output channel sampled at least min(its element count, 500) times."""
+        x_hat = self._decode_frame(y_hat, mean=mean, std=std, channels=channels, box=box)
         D = self.cfg['embed_dim']
-        return x_hat, self._to_host("ok1", self._probe(self._buf(f"t{D}", (self.Hp * self.Wp, D)), (x_hat, 2053)))
+        stride = 2053 if channels is None and box is None else max(1, (x_hat.numel() // x_hat.shape[0]) // 500)
+        return x_hat, self._to_host("ok1", self._probe(self._buf(f"t{D}", (self.Hp * self.Wp, D)), (x_hat, stride)))
 
-    def _decode_guarded(self, y_hat, mean=None, std=None):
-        """g_s of one frame under the range guard: y_hat [L, Hp, Wp] -> x_hat [C, H, W]."""
+    def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None):
+        """g_s of one frame under the range guard: y_hat [L, Hp, Wp] -> x_hat [C, H, W] (or its subset: canonical
+        channels / box of _subset_args)."""
         def run():
             with self._gpu_phase():
-                x_hat, flag = self._g_s_probed(y_hat, mean, std)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, run, "decode")
 
@@ -974,10 +1107,13 @@ class VAEformer(nn.Module):
         return y, None, None
 
     @torch.no_grad()
-    def decode_latent(self, y, type='quantized'):
-        """vaeformer.py:294-300."""
+    def decode_latent(self, y, type='quantized', channels=None, box=None):
+        """vaeformer.py:294-300.  channels: output channel indices (in the order given); box = (r0, r1, c0, nc): grid rows
+        [r0, r1) and nc columns from c0, wrapping at W (subset.grid_box) -> [B, len(channels), r1 - r0, nc], the same
+        slice of the full decode bit for bit."""
         self._require_gpu()
-        return torch.stack([self._decode_guarded(y[b]) for b in range(y.shape[0])])
+        channels, box = self._subset_args(channels, box)
+        return torch.stack([self._decode_guarded(y[b], channels=channels, box=box) for b in range(y.shape[0])])
 
     @torch.no_grad()
     def forward(self, x):
@@ -1114,8 +1250,9 @@ class VAEformer(nn.Module):
             "(a .bin written by the PyTorch reference or by another engine; DESIGN.md section 2).  A damaged y "
             "stream or a different checkpoint looks the same.  Nothing was reconstructed", e.status)
 
-    def _decompress_frame(self, y_string, z_string, shape, reconstruct, mean=None, std=None):
-        """host: decode z | GPU: h_s, indexes | host: decode y | GPU: de-quantise (+ g_s)."""
+    def _decompress_frame(self, y_string, z_string, shape, reconstruct, mean=None, std=None, channels=None, box=None):
+        """host: decode z | GPU: h_s, indexes | host: decode y | GPU: de-quantise (+ g_s: the whole frame, or the
+        canonical channels / box of _subset_args)."""
         eb, gc = self.entropy_bottleneck, self.gaussian_conditional
         Cz = eb.channels
         zh, zw = int(shape[0]), int(shape[1])
@@ -1190,19 +1327,23 @@ class VAEformer(nn.Module):
                     y_hat = ops.gaussian_conditional(scales, means, gc.scale_table, sym_in=y_sym, want=("y_hat",))["y_hat"]
                 if not reconstruct:
                     return y_hat, True, None
-                x_hat, flag = self._g_s_probed(y_hat, mean, std)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, gpu_side, "decompress")
 
     @torch.no_grad()
-    def decompress(self, strings, shape, return_format='reconstructed'):
-        """vaeformer.py:378-400."""
+    def decompress(self, strings, shape, return_format='reconstructed', channels=None, box=None):
+        """vaeformer.py:378-400.  channels / box: a subset of the reconstruction (decode_latent)."""
         self._require_gpu()
         assert isinstance(strings, list) and len(strings) == 2
+        rec = return_format != 'latent'
+        if not rec and (channels is not None or box is not None):
+            raise ValueError("decompress: return_format='latent' returns the latent; channels / box select a subset "
+                             "of the reconstruction")
+        channels, box = self._subset_args(channels, box)
         self.entropy_bottleneck._check()
         self.gaussian_conditional._check()
-        rec = return_format != 'latent'
-        out = torch.stack([self._decompress_frame(strings[0][b], strings[1][b], shape, rec)
+        out = torch.stack([self._decompress_frame(strings[0][b], strings[1][b], shape, rec, channels=channels, box=box)
                            for b in range(len(strings[0]))])
         if not rec:
             return out

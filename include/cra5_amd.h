@@ -146,6 +146,12 @@ int cra5_pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *
 #define CRA5_GEMM_A_PLAIN 16
 #define CRA5_GEMM_W_PLAIN 32
 #define CRA5_GEMM_OUT_PLAIN 64
+/* With CRA5_GEMM_HI_ONLY and Kp % 64 == 0 (CRA5_ERR_ARG otherwise): take the wide form - 64-wide k-steps, the
+ * summation order of every launch with >= 256 128 x 128 tiles - whatever the problem size.  A slice of such a GEMM
+ * computed on its own (the rows / columns of a subset decode) then rounds exactly like the big launch; without the flag
+ * a smaller problem takes the 32-wide k-step form, whose other summation order rounds differently.  Plain operands are
+ * accepted at any size with it. */
+#define CRA5_GEMM_WIDE_K 128
 int cra5_gemm_nt_f32(const float *A, int lda, const float *W, int ldw, float *C, int ldc,
                      const float *bias, const float *res, int ldr, int M, int N, int K,
                      int flags, void *stream);
@@ -262,6 +268,18 @@ int cra5_im2col_f32(const float *x, const float *mean, const float *std, float *
 int cra5_col2im_f32(const float *cols, const float *mean, const float *std, float *x, int C,
                     int H, int W, int kh, int kw, int sh, int sw, int Hp, int Wp, int ldn,
                     void *stream);
+
+/* Subset decode (csrc/subset.hip): the two copies around the un-embed of a patch-aligned superset of a lat/lon box.
+ * cra5_gather_token_rows: dst row r = i * n_tj + j (i < n_ti, j < n_tj) <- src row (ti0 + i) * Wp + (tj0 + j) mod Wp of a
+ * token-major matrix of Hp * Wp rows (the token columns wrap at the grid's east edge); `row_bytes` bytes per row copied
+ * verbatim (split-f16, plain f16 or fp32 rows alike).  row_bytes, both pitches and both pointers 16-byte aligned;
+ * 0 <= ti0, ti0 + n_ti <= Hp, 0 <= tj0 < Wp, 1 <= n_tj <= Wp - CRA5_ERR_ARG otherwise.
+ * cra5_crop_f32: dst[c][i][j] = src[c][r0 + i][(c0 + j) mod Ws] for c < C, i < Hb, j < Wb; src [C][Hs][Ws], dst
+ * [C][Hb][Wb], both contiguous, any element offset.  0 <= r0, r0 + Hb <= Hs, 0 <= c0 < Ws, 1 <= Wb <= Ws - CRA5_ERR_ARG
+ * otherwise. */
+int cra5_gather_token_rows(const void *src, size_t src_pitch_bytes, void *dst, size_t dst_pitch_bytes,
+                           size_t row_bytes, int Hp, int Wp, int ti0, int n_ti, int tj0, int n_tj, void *stream);
+int cra5_crop_f32(const float *src, int C, int Hs, int Ws, float *dst, int r0, int Hb, int c0, int Wb, void *stream);
 
 /* Finiteness probe of the range guard: partials[b] = sum of x[i * stride] over block b's share of i = 0 .. ceil(n / stride)
  * - 1, b = 0 .. CRA5_PROBE_PARTIALS - 1 (written, never accumulated: no memset, deterministic).  A partial is non-finite as
