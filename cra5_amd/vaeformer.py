@@ -557,10 +557,14 @@ class VAEformer(nn.Module):
         """PLAIN f16 copy of a weight (the hi plane of its split copy, same power-of-two scale), cached."""
         return self._derive("wpl." + key, w, lambda _w: self._wsplit(key, w).plain_copy())
 
+    def _hi(self, key):
+        """Does the reduced-precision mode (one f16 product, hi_only) apply to the g_a / g_s launch `key`?"""
+        return self.precision == "f16" and key.startswith(("g_a.", "g_s."))
+
     def _plain_gemm(self, key, M, N, K):
         """Does the reduced-precision GEMM `key` of shape M x N x K run on plain-f16 operands?"""
-        return (self.precision == "f16" and self.f16_layout == "plain" and self.gemm_mode == "split"
-                and key.startswith(("g_a.", "g_s.")) and ops.plain_ok(M, N, _rup(K, 32)))
+        return (self._hi(key) and self.f16_layout == "plain" and self.gemm_mode == "split"
+                and ops.plain_ok(M, N, _rup(K, 32)))
 
     def _wf32(self, key, w, pad32=False):
         w2 = self._weight2d(key, w)
@@ -593,7 +597,7 @@ class VAEformer(nn.Module):
         result's rows are plain f16 (the caller has checked that its consumer takes them)."""
         if self.gemm_mode == "split":
             W = self._wsplit(key, w)
-            hi = self.precision == "f16" and key.startswith(("g_a.", "g_s."))
+            hi = self._hi(key)
             if self._plain_gemm(key, a.rows, W.rows, W.K):
                 W = self._wplain(key, w)
             else:
@@ -623,11 +627,13 @@ class VAEformer(nn.Module):
         p_qkv, p_proj = (self._plain_gemm(pre + ".attn.qkv", N, 3 * D, D), self._plain_gemm(pre + ".attn.proj", N, D, D))
         p_fc1, p_fc2 = (self._plain_gemm(pre + ".mlp.fc1", N, 4 * D, D), self._plain_gemm(pre + ".mlp.fc2", N, D, 4 * D))
         h = self._ln(t_in, blk.norm1, f"h{D}", plain=p_qkv)
+        # fused split attention: qkv never exists in fp32 (GEMM epilogue -> split-f16 -> f16-MFMA attention -> split);
+        # the other attention kernels read an fp32 qkv workspace
+        qkv = self._mm(h, pre + ".attn.qkv", blk.attn.qkv.weight, bias=blk.attn.qkv.bias,
+                       out=None if fused_attn else self._buf(f"qkv{D}", (N, 3 * D)),
+                       out_name=f"qkv{D}" if fused_attn else None, out_plain=fused_attn and p_qkv and p_proj)
         if fused_attn:
-            # qkv never exists in fp32: GEMM epilogue -> split-f16 -> f16-MFMA attention -> split
-            qkv_s = self._mm(h, pre + ".attn.qkv", blk.attn.qkv.weight, bias=blk.attn.qkv.bias, out_name=f"qkv{D}",
-                             out_plain=p_qkv and p_proj)
-            if qkv_s.plain:
+            if qkv.plain:
                 pad_s = self._derive("padp." + pre, blk.attn.qkv.bias, lambda b: ops.split_f16(b.reshape(1, -1)).plain_copy())
             else:
                 pad_s = self._derive("pad." + pre, blk.attn.qkv.bias, lambda b: ops.split_f16(b.reshape(1, -1)))
@@ -638,25 +644,19 @@ class VAEformer(nn.Module):
                 # only the hyper-prior path, which never takes this branch, must be bit-stable across the codec's sides)
                 bal, nb = ops.attention_balanced_plan(N, blk.heads)
                 ws = self._buf("attn_ws", (nb,), torch.uint8) if (bal and nb) else None
-            ops.window_attention_split(qkv_s, pad_s, blk.heads, H, W, wh, ww, out_split=att, workspace=ws, balanced=bal,
-                                       hi_only=self.precision == "f16" and pre.startswith(("g_a.", "g_s.")))
-            self._mm(att, pre + ".attn.proj", blk.attn.proj.weight, bias=blk.attn.proj.bias, res=t_in, out=t_out)
-            h = self._ln(t_out, blk.norm2, f"h{D}", plain=p_fc1)
-            hid = self._mm(h, pre + ".mlp.fc1", blk.mlp.fc1.weight, bias=blk.mlp.fc1.bias, gelu=True,
-                           out_name=f"hid{D}", out_plain=p_fc1 and p_fc2)
-            self._mm(hid, pre + ".mlp.fc2", blk.mlp.fc2.weight, bias=blk.mlp.fc2.bias, res=t_out, out=t_out)
-            return t_out
-        qkv = self._mm(h, pre + ".attn.qkv", blk.attn.qkv.weight, bias=blk.attn.qkv.bias,
-                       out=self._buf(f"qkv{D}", (N, 3 * D)))
-        if split:
+            ops.window_attention_split(qkv, pad_s, blk.heads, H, W, wh, ww, out_split=att, workspace=ws, balanced=bal,
+                                       hi_only=self._hi(pre))
+        elif split:
             att = self._sbuf(f"att{D}", N, D, zero=True)   # pad columns stay zero
             ops.window_attention(qkv, blk.attn.qkv.bias, blk.heads, H, W, wh, ww, out_split=att, want_f32=False)
         else:
             att = ops.window_attention(qkv, blk.attn.qkv.bias, blk.heads, H, W, wh, ww,
                                        out=self._buf(f"att{D}", (N, D)))
         self._mm(att, pre + ".attn.proj", blk.attn.proj.weight, bias=blk.attn.proj.bias, res=t_in, out=t_out)
-        h = self._ln(t_out, blk.norm2, f"h{D}")
-        hid = self._mm(h, pre + ".mlp.fc1", blk.mlp.fc1.weight, bias=blk.mlp.fc1.bias, gelu=True, out_name=f"hid{D}")
+        # plain rows into fc1 / fc2 on the fused-attention branch only (the other branch keeps split rows)
+        h = self._ln(t_out, blk.norm2, f"h{D}", plain=fused_attn and p_fc1)
+        hid = self._mm(h, pre + ".mlp.fc1", blk.mlp.fc1.weight, bias=blk.mlp.fc1.bias, gelu=True,
+                       out_name=f"hid{D}", out_plain=fused_attn and p_fc1 and p_fc2)
         self._mm(hid, pre + ".mlp.fc2", blk.mlp.fc2.weight, bias=blk.mlp.fc2.bias, res=t_out, out=t_out)
         return t_out
 
@@ -789,12 +789,10 @@ class VAEformer(nn.Module):
     # ---- g_s --------------------------------------------------------------------------------
     def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None):
         """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300).  channels / box (canonical, _subset_args): the
-        [len(channels), r1 - r0, nc] slice of that frame, bit for bit (_unembed_subset)."""
+        [len(channels), r1 - r0, nc] slice of that frame, bit for bit (_unembed)."""
         cfg = self.cfg
         D, L = cfg['embed_dim'], cfg['latent_dim']
         N = self.Hp * self.Wp
-        kh, kw = cfg['patch_size']
-        sh, sw = cfg['patch_stride']
         ytok = self._buf("ytok", (N, L))
         ops.transpose(y_hat.reshape(L, N), out=ytok)
         t = self._buf(f"t{D}", (N, D))
@@ -803,29 +801,11 @@ class VAEformer(nn.Module):
         for j, blk in enumerate(self.g_s.blocks):
             self._block(blk, f"g_s.blocks.{j}", t, t, (self.Hp, self.Wp))
         Cout, (Himg, Wimg) = cfg['out_chans'], cfg['img_size']
-        # reduced-precision mode: the fused un-embed (always the 256 x 256 wide form) takes plain operands when D % 64 == 0
-        p_ue = (self.precision == "f16" and self.f16_layout == "plain" and self.gemm_mode == "split" and D % 64 == 0
-                and self.fused_unembed and D <= 8192 and ops.unembed_side_bytes(Cout, Himg, Wimg, kh, kw, sh, sw) > 0)
-        h = self._ln(t, self.g_s.norm, f"h{D}", plain=p_ue)
-        if channels is not None or box is not None:
-            return self._unembed_subset(h, mean, std, channels, box)
-        x_hat = torch.empty((Cout, Himg, Wimg), device=self.device, dtype=torch.float32)
-        nside = ops.unembed_side_bytes(Cout, Himg, Wimg, kh, kw, sh, sw) if self.gemm_mode == "split" else 0
-        if nside and self.fused_unembed and D <= 8192:
-            # ONE fused launch pair: the GEMM epilogue scatters into the reconstruction (de-normalised), the overlap
-            # rows go through a 2-rows-per-patch-row side buffer (no [tokens][C*110] column matrix, no overlap-add pass)
-            side = self._buf("ue_side", (nside // 4,))
-            wue = self._wplain("g_s.final", self.g_s.final.weight) if p_ue else self._wsplit("g_s.final", self.g_s.final.weight)
-            ops.gemm_unembed(h, wue, Cout, Himg, Wimg, kh, kw, sh, sw, side,
-                             mean=mean, std=std, out=x_hat, hi_only=self.precision == "f16")
-            return x_hat
-        ncol = Cout * kh * kw
-        cols = self._buf("ue_cols", (N, ncol))
-        self._mm(h, "g_s.final", self.g_s.final.weight, out=cols)
-        ops.col2im(cols, Cout, kh, kw, sh, sw, self.Hp, self.Wp, mean=mean, std=std, out=x_hat)
-        return x_hat
+        # the LayerNorm writes plain rows when the whole frame's un-embed would take them (a subset's geometry may not)
+        h = self._ln(t, self.g_s.norm, f"h{D}", plain=self._fused_unembed_form(Cout, Himg, Wimg)[1])
+        return self._unembed(h, mean, std, channels, box)
 
-    # ---- subset decode: chosen channels and / or a lat-lon box of the reconstruction ------------------------
+    # ---- un-embed: the whole frame, or chosen channels and / or a lat-lon box of it ---------------------------
     # The transformer runs on the whole grid (global attention); everything after the final LayerNorm is local.  The
     # un-embed runs on the patch-aligned superset of tokens whose patches reach the box (subset.token_plan) with the
     # chosen channels' weight rows, and a crop cuts the box out of the superset image: the same kernels on the same
@@ -893,20 +873,38 @@ class VAEformer(nn.Module):
         return self._sub_cached(("stat", t.data_ptr(), t._version, chans), t,
                                 lambda: t.index_select(0, torch.tensor(chans, device=t.device, dtype=torch.long)))
 
-    def _unembed_subset(self, h, mean, std, chans, box):
-        """The un-embed of decode_frame for channels `chans` (tuple | None) inside grid box `box` (tuple | None), from
-        the final LayerNorm's output h (SplitMat, or fp32 [N, D] on the exact-f32 engines) -> a fresh [C', Hb, Wb]."""
+    def _fused_unembed_form(self, C, H, W):
+        """The un-embed of a [C, H, W] image: -> (nside, plain).  nside > 0: ONE fused launch pair runs - the GEMM
+        epilogue scatters into the image (de-normalised), the overlap rows go through a side buffer of nside bytes (no
+        [tokens][C*kh*kw] column matrix, no overlap-add pass); 0: the two-call form (GEMM + col2im).  plain: the fused
+        launch (always the 256 x 256 wide form) takes plain-f16 A rows (reduced precision, plain layout, D % 64 == 0)."""
+        cfg = self.cfg
+        D = cfg['embed_dim']
+        (kh, kw), (sh, sw) = cfg['patch_size'], cfg['patch_stride']
+        nside = (ops.unembed_side_bytes(C, H, W, kh, kw, sh, sw)
+                 if self.gemm_mode == "split" and self.fused_unembed and D <= 8192 else 0)
+        return nside, bool(nside) and self._hi("g_s.final") and self.f16_layout == "plain" and D % 64 == 0
+
+    def _unembed(self, h, mean, std, chans, box):
+        """The un-embed for channels `chans` (tuple | None: all) inside grid box `box` (tuple | None: the whole grid),
+        from the final LayerNorm's output h (SplitMat, or fp32 [N, D] on the exact-f32 engines) -> a fresh [C', Hb, Wb].
+        chans = box = None is the full decode."""
         cfg = self.cfg
         D = cfg['embed_dim']
         kh, kw = cfg['patch_size']
         sh, sw = cfg['patch_stride']
         Cout, (Himg, Wimg) = cfg['out_chans'], cfg['img_size']
-        p = subset.token_plan(box if box is not None else (0, Himg, 0, Wimg), Himg, Wimg, kh, kw, sh, sw)
+        Hp, Wp = self.Hp, self.Wp
+        if box is None:    # (built here: token_plan knows only the ERA5 geometry, the whole grid needs none)
+            p = dict(ti0=0, n_ti=Hp, tj0=0, n_tj=Wp, Hs=Himg, Ws=Wimg, Hb=Himg, Wb=Wimg, exact=True)
+        else:
+            p = subset.token_plan(box, Himg, Wimg, kh, kw, sh, sw)
+        sub = "" if chans is None and box is None else "_sub"   # (a thread alternating the two keeps both workspaces)
         Cs = len(chans) if chans is not None else Cout
         ms, ss = self._stats_of_channels(mean, chans), self._stats_of_channels(std, chans)
         split = self.gemm_mode == "split"
         # A operand: the superset's token rows, verbatim.  A latitude band over the whole circle is a run of rows.
-        M, Hp, Wp = p["n_ti"] * p["n_tj"], self.Hp, self.Wp
+        M = p["n_ti"] * p["n_tj"]
         if p["n_tj"] == Wp:
             r = slice(p["ti0"] * Wp, p["ti0"] * Wp + M)
             a = ops.SplitMat(h.data[r], M, h.K, h.Kp, h.scale_inv, plain=h.plain) if split else h[r]
@@ -917,26 +915,26 @@ class VAEformer(nn.Module):
         out = torch.empty((Cs, p["Hb"], p["Wb"]), device=self.device, dtype=torch.float32)
         sup = out if p["exact"] else self._buf("ue_sup", (Cs, Hs, Ws))
         key, w = "g_s.final", self.g_s.final.weight
-        nside = ops.unembed_side_bytes(Cs, Hs, Ws, kh, kw, sh, sw) if split else 0
-        if nside and self.fused_unembed and D <= 8192:
-            # the full decode's fused launch pair, unchanged, on the superset geometry (H = 10 n_ti + 1, W = 10 n_tj)
-            side = self._buf("ue_side_sub", (nside // 4,))
+        nside = self._fused_unembed_form(Cs, Hs, Ws)[0]
+        if nside:
+            # a subset runs the full decode's launch pair on the superset geometry (H = 10 n_ti + 1, W = 10 n_tj)
+            side = self._buf("ue_side" + sub, (nside // 4,))
             wfull = self._wplain(key, w) if h.plain else self._wsplit(key, w)
             wue = wfull if chans is None else self._rows_of_channels("plain" if h.plain else "split", wfull, chans)
-            ops.gemm_unembed(a, wue, Cs, Hs, Ws, kh, kw, sh, sw, side, mean=ms, std=ss, out=sup,
-                             hi_only=self.precision == "f16")
+            ops.gemm_unembed(a, wue, Cs, Hs, Ws, kh, kw, sh, sw, side, mean=ms, std=ss, out=sup, hi_only=self._hi(key))
         else:
-            cols = self._buf("ue_cols_sub", (M, Cs * kh * kw))
+            cols = self._buf("ue_cols" + sub, (M, Cs * kh * kw))
             if split:
-                # the full decode's GEMM (_mm) is ONE launch of M = Hp * Wp tokens x N = C * kh * kw columns: the weight
-                # copy it reads and its summation order are those of that shape, whatever the subset's size
+                # the full decode's GEMM is ONE launch of M = Hp * Wp tokens x N = C * kh * kw columns: a subset reads
+                # the weight copy of that shape and takes its summation order (CRA5_GEMM_WIDE_K), whatever its own size.
+                # The full launch itself sets no flag: it takes that form by its size (and the flag refuses Kp > 8192).
                 Mf, Nf = Hp * Wp, Cout * kh * kw
                 wsp = self._wsplit(key, w)
-                hi = self.precision == "f16"
+                hi = self._hi(key)
                 kind = "plain" if self._plain_gemm(key, Mf, Nf, wsp.K) else "split"
                 wfull = self._wplain(key, w) if kind == "plain" else wsp
                 wg = wfull if chans is None else self._rows_of_channels(kind, wfull, chans)
-                ops.gemm_nt_split(a, wg, out=cols, hi_only=hi, wide_k=hi and ops.plain_ok(Mf, Nf, wsp.Kp))
+                ops.gemm_nt_split(a, wg, out=cols, hi_only=hi, wide_k=hi and sub != "" and ops.plain_ok(Mf, Nf, wsp.Kp))
             else:
                 wf = self._wf32(key, w)
                 wg = wf if chans is None else self._rows_of_channels("f32", wf, chans)
