@@ -201,20 +201,25 @@ class cra5_api:
     # variables=[names] and / or region=(lat_min, lat_max, lon_min, lon_max) in degrees: the decode returns those channels
     # (in the order given) over that box - the same values as the slice of a full decode, bit for bit - and only the
     # subset is written on the GPU, crosses the host link and lands in host memory ("Subset decode").
+    # stride=s or (s_lat, s_lon): of that box (default: the globe) only the rows r with r % s_lat == 0 and the columns c
+    # with c % s_lon == 0, r / c counted on the GLOBAL grid - stride=6 is the 121 x 240 grid at 1.5 deg, poles included.
+    # No interpolation, no averaging: with `full` the full decode of the same file under the same settings,
+    # x_hat == full[channels][:, kept_rows][:, :, kept_cols] as bit patterns.  None / 1 / (1, 1): no thinning.
     grid_box = staticmethod(subset.grid_box)
     resolve_variables = staticmethod(subset.resolve_variables)
 
-    def _subset(self, variables, region):
-        """-> (channel indices | None, grid box | None, the result dict's extra keys) for the model; (None, None, None)
-        without a subset."""
-        if variables is None and region is None:
-            return None, None, None
+    def _subset(self, variables, region, stride=None):
+        """-> (channel indices | None, grid box | None, stride (s_lat, s_lon) | None, the result dict's extra keys) for
+        the model; (None, None, None, None) without a subset."""
         H, W = self.net.cfg['img_size']
+        step = subset.resolve_stride(stride, W)
+        if variables is None and region is None and step is None:
+            return None, None, None, None
         chans = subset.resolve_variables(variables, self.vname_to_channels)
-        g = subset.grid_box(region if region is not None else (-90.0, 90.0, 0.0, 360.0), H, W)
+        g = subset.grid_box(region if region is not None else (-90.0, 90.0, 0.0, 360.0), H, W, stride=step)
         names = [self.channels_to_vname.get(c, str(c)) for c in (chans if chans is not None else range(self.net.cfg['out_chans']))]
         channels, box = self.net._subset_args(chans, g["box"] if region is not None else None)
-        return channels, box, dict(variables=names, lat=g["lat"], lon=g["lon"])
+        return channels, box, self.net._step_arg(step, box), dict(variables=names, lat=g["lat"], lon=g["lon"])
 
     def get_mean_std(self):
         """cra5_api.py:243-261."""
@@ -477,15 +482,17 @@ class cra5_api:
         return self._pipeline(workers).map(lambda it: self._encode_one(it[0], it[1], save_root, write),
                                            list(zip(time_stamps, frames)))
 
-    def _decode_one(self, i, path, denorm, out=None, sink=None, channels=None, box=None):
+    def _decode_one(self, i, path, denorm, out=None, sink=None, channels=None, box=None, step=None):
         """One frame of the batch decode on the calling frame thread: .bin -> x_hat (or its subset: canonical channels /
-        box of VAEformer._subset_args) -> this thread's pinned buffer -> `sink` / `out[i]` / a fresh array."""
+        box / step of VAEformer._subset_args / _step_arg) -> this thread's pinned buffer -> `sink` / `out[i]` / a fresh
+        array."""
         lstrings, shape = self._read_bin(path)
         with torch.no_grad():
             t_d = time.perf_counter()
             x_hat = self.net._decompress_frame(lstrings[0][0], lstrings[1][0], shape, True,
                                                mean=self._mean_flat if denorm else None,
-                                               std=self._std_flat if denorm else None, channels=channels, box=box)
+                                               std=self._std_flat if denorm else None, channels=channels, box=box,
+                                               step=step)
             self._log("decompress", t_d)
             C, H, W = x_hat.shape[-3:]
             pin = self.net._pinned("api_x_out", (C, H, W), torch.float32)
@@ -543,28 +550,29 @@ class cra5_api:
         return self._pipeline(workers).map(one, [(i, ts, a) for i, (ts, a) in enumerate(zip(time_stamps, frames))])
 
     def decode_batch(self, time_stamps=None, paths=None, return_format='de_normalized', out=None, workers=12, sink=None,
-                     variables=None, region=None):
+                     variables=None, region=None, stride=None):
         """decode_from_bin for many frames.  Returns a list of HOST float32 arrays [C, H, W] (views of `out`
         [n, C, H, W] when given, fresh arrays otherwise); the D2H of each reconstruction goes through the
         decoding thread's pinned buffer and overlaps the other frames' work.  `sink(i, frame)`: called on the decoding
         thread with frame i as a [C, H, W] float32 view of that thread's PINNED buffer (valid until the call returns:
         write it to disk, reduce it, copy it) instead of copying it out; the list then holds the sink's return values -
         a long decode loop needs no [n, C, H, W] host array.
-        variables / region (decode_from_bin): every frame is the subset [C', Hb, Wb] - `out` must then be
-        [n, C', Hb, Wb], `sink` gets [C', Hb, Wb] views; grid_box(region) gives its lat / lon."""
+        variables / region / stride (decode_from_bin): every frame is the subset [C', Hb, Wb] - `out` must then be
+        [n, C', Hb, Wb], `sink` gets [C', Hb, Wb] views; grid_box(region, stride=stride) gives its lat / lon (with a
+        stride Hb / Wb count the kept rows / columns: stride=6 over the globe is [C', 121, 240])."""
         if paths is None:
             paths = [f'{self.local_root}/CRA5/{ts[:4]}/{ts}.bin' for ts in time_stamps]
         if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
             raise ValueError(f"unknown return_format {return_format!r}")
         denorm = return_format != 'normalized'
         self.net._require_gpu()
-        channels, box, meta = self._subset(variables, region)
+        channels, box, step, meta = self._subset(variables, region, stride)
         shape = None
         if meta is not None:
             shape = (len(meta["variables"]), len(meta["lat"]), len(meta["lon"]))
         self._check_out(out, len(paths), shape)
 
-        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box),
+        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box, step),
                                            list(enumerate(paths)))
 
     def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights):
@@ -641,26 +649,31 @@ class cra5_api:
         with torch.no_grad():
             return self.net.decompress(lstrings, shape, return_format='latent')
 
-    def latent_to_reconstruction(self, y_hat, variables=None, region=None):
-        """cra5_api.py:146-151 (normalised units).  variables / region: that subset (decode_from_bin)."""
-        channels, box, _ = self._subset(variables, region)
+    def latent_to_reconstruction(self, y_hat, variables=None, region=None, stride=None):
+        """cra5_api.py:146-151 (normalised units).  variables / region / stride: that subset (decode_from_bin)."""
+        channels, box, step, _ = self._subset(variables, region, stride)
         with torch.no_grad():
-            return self.net.decode_latent(y_hat, channels=channels, box=box)
+            return self.net.decode_latent(y_hat, channels=channels, box=box, step=step)
 
     def decode_from_bin(self, time_stamp=None, custom_path=None, return_format='de_normalized', to_host=False, out=None,
-                        variables=None, region=None):
+                        variables=None, region=None, stride=None):
         """cra5_api.py:153-192.  `to_host=True` (or `out=` a float32 array of the frame's shape): `x_hat` comes back
         as a HOST numpy array through the pinned staging buffer instead of a device tensor.
         variables: names of channel_vname_mapping() (e.g. ["z_500", "t_850", "t2m"]), output channels in that order;
         region: (lat_min, lat_max, lon_min, lon_max) in degrees (grid_box).  Either gives x_hat [C', Hb, Wb] - the slice
         of the full decode, bit for bit - and the dict then also carries `variables`, `lat` and `lon` (float64, lon in
-        [0, 360))."""
-        if return_format == 'latent' and (variables is not None or region is not None):
-            raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region select a "
-                             "subset of the reconstruction")
+        [0, 360)).
+        stride: a positive int or (s_lat, s_lon) - of the box (default: the globe) only the rows r with r % s_lat == 0 and
+        the columns c with c % s_lon == 0, r / c counted on the GLOBAL grid (a region's thinned decode is a sub-block of the
+        globe's; 1440 % s_lon must be 0): decode_from_bin(ts, stride=6) is the 121 x 240 grid at 1.5 deg.  Again the slice
+        of the full decode, bit for bit: x_hat == full[channels][:, kept_rows][:, :, kept_cols]; `lat` / `lon` are those of
+        the kept rows / columns, `out` is checked against the thinned shape.  None / 1 / (1, 1): no thinning."""
+        if return_format == 'latent' and (variables is not None or region is not None or stride is not None):
+            raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region / stride "
+                             "select a subset of the reconstruction")
         if return_format not in ('latent', 'normalized', 'de_normalized', 'de_normlized'):
             raise ValueError(f"unknown return_format {return_format!r}")
-        channels, box, meta = self._subset(variables, region)
+        channels, box, step, meta = self._subset(variables, region, stride)
         bin_path = custom_path or f'{self.local_root}/CRA5/{time_stamp[:4]}/{time_stamp}.bin'
         decoding_start = time.time()
         lstrings, shape = self._read_bin(bin_path)
@@ -669,11 +682,11 @@ class cra5_api:
             if return_format == 'latent':
                 return y_hat
             if return_format == 'normalized':
-                x_hat = self.net.decode_latent(y_hat, channels=channels, box=box)
+                x_hat = self.net.decode_latent(y_hat, channels=channels, box=box, step=step)
             else:
                 # fused de-normalisation in the overlap-add store
                 x_hat = self.net._decode_guarded(y_hat[0], mean=self._mean_flat, std=self._std_flat, channels=channels,
-                                                 box=box)
+                                                 box=box, step=step)
             if to_host or out is not None:
                 src = x_hat.reshape(x_hat.shape[-3:]).contiguous()
                 if out is None:

@@ -583,10 +583,12 @@ def col2im(cols, C, kh, kw, sh, sw, Hp, Wp, mean=None, std=None, out=None):
     return out
 
 
-def gather_token_rows(src, out, Hp, Wp, ti0, n_ti, tj0, n_tj):
+def gather_token_rows(src, out, Hp, Wp, ti0, n_ti, tj0, n_tj, ti_step=None, tj_step=None):
     """cra5_gather_token_rows: rows (ti0 + i) * Wp + (tj0 + j) mod Wp (i < n_ti, j < n_tj) of the token-major matrix `src`
     (Hp * Wp rows) -> rows i * n_tj + j of `out`, verbatim.  src / out: both SplitMat (split or plain rows; `out` takes
-    src's layout) or both 2-D fp32 device tensors with unit inner stride."""
+    src's layout) or both 2-D fp32 device tensors with unit inner stride.
+    ti_step / tj_step (both given): cra5_gather_token_lattice - rows (ti0 + i * ti_step) * Wp + (tj0 + j * tj_step) mod Wp,
+    the strided lattice of one token class of a thinned decode (subset.stride_plan)."""
     if isinstance(src, SplitMat):
         if not isinstance(out, SplitMat) or out.Kp != src.Kp or out.K != src.K or out.rows != n_ti * n_tj:
             raise ValueError("gather_token_rows: `out` must be a SplitMat of n_ti * n_tj rows and src's K")
@@ -604,8 +606,40 @@ def gather_token_rows(src, out, Hp, Wp, ti0, n_ti, tj0, n_tj):
     if s_t.shape[0] != Hp * Wp:
         raise ValueError(f"gather_token_rows: src has {s_t.shape[0]} rows, the grid {Hp} x {Wp} tokens")
     es = s_t.element_size()
+    if (ti_step is None) != (tj_step is None):
+        raise ValueError("gather_token_rows: ti_step and tj_step come together")
+    if ti_step is not None:
+        check(lib().cra5_gather_token_lattice(_p(s_t), _row_stride(s_t) * es, _p(d_t), _row_stride(d_t) * es, row_bytes,
+                                              Hp, Wp, ti0, ti_step, n_ti, tj0, tj_step, n_tj, _stream()),
+              "cra5_gather_token_lattice")
+        return out
     check(lib().cra5_gather_token_rows(_p(s_t), _row_stride(s_t) * es, _p(d_t), _row_stride(d_t) * es, row_bytes, Hp, Wp,
                                        ti0, n_ti, tj0, n_tj, _stream()), "cra5_gather_token_rows")
+    return out
+
+
+def strided_scatter(g, rows, cols, cls, n_cc, C, mean=None, std=None, out=None):
+    """cra5_strided_scatter_f32: the thinned image [C, Ho, Wo] from the class matrices in the flat fp32 workspace `g`;
+    rows int32 [Ho, 6], cols int32 [Wo, 3], cls int64 [n_rc * n_cc, 5]: device copies of subset.scatter_tables.  A seam
+    row's point is its upper + lower partner, in that order; mean / std [C]: de-normalised (x * std[c] + mean[c])."""
+    _dev(g, mean, std, out)
+    ok = (g.is_contiguous() and g.dim() == 1 and all(t.is_cuda and t.is_contiguous() for t in (rows, cols, cls))
+          and rows.dtype == torch.int32 and cols.dtype == torch.int32 and cls.dtype == torch.int64
+          and rows.dim() == 2 and rows.shape[1] == 6 and cols.dim() == 2 and cols.shape[1] == 3
+          and cls.dim() == 2 and cls.shape[1] == 5 and n_cc > 0 and cls.shape[0] % n_cc == 0)
+    if not ok:
+        raise ValueError("strided_scatter: g is a flat fp32 workspace; rows [Ho, 6] / cols [Wo, 3] int32 and cls "
+                         "[n_rc * n_cc, 5] int64 contiguous device tables (subset.scatter_tables)")
+    Ho, Wo = rows.shape[0], cols.shape[0]
+    if out is None:
+        out = torch.empty((C, Ho, Wo), device=g.device, dtype=torch.float32)
+    if not (out.is_contiguous() and tuple(out.shape) == (C, Ho, Wo)):
+        raise ValueError(f"strided_scatter: out must be a contiguous [{C}, {Ho}, {Wo}] tensor")
+    ev = TIMER.start() if TIMER is not None else None
+    check(lib().cra5_strided_scatter_f32(_p(g), g.numel(), _p(rows), _p(cols), _p(cls), cls.shape[0] // n_cc, n_cc,
+                                         _p(mean), _p(std), _p(out), C, Ho, Wo, _stream()), "cra5_strided_scatter_f32")
+    if ev is not None:
+        TIMER.stop("strided_scatter", ev, 8.0 * C * Ho * Wo)
     return out
 
 

@@ -2,19 +2,61 @@
 
 Host-side geometry only (no model, no GPU): `grid_box` turns a lat/lon box in degrees into grid rows / columns,
 `resolve_variables` turns variable names into channel indices, `token_plan` gives the patch-aligned superset of tokens the
-un-embed runs on for a box (VAEformer._decode_frame; DESIGN.md, "Subset decode").
+un-embed runs on for a box (VAEformer._decode_frame; DESIGN.md, "Subset decode").  `resolve_stride`, `kept_points`,
+`stride_plan` and `scatter_tables` are the geometry of a thinned grid (every s_lat-th row, every s_lon-th column of the
+global grid): which (token, tap) products of the un-embed a thinned box needs and where each lands.
 
 Grid convention (metrics.latitude_weights): row h is latitude 90 - h * 180 / (H - 1) (row 0 = 90 N), column w is longitude
 w * 360 / W (column 0 = Greenwich, eastward).
 """
 import math
+import operator
 
 import numpy as np
 
 TOL_DEG = 1e-9        # a bound within this many degrees of a grid point is on it
 
 
-def grid_box(region, H=721, W=1440):
+def resolve_stride(stride, W=1440):
+    """stride: None | a positive int | a pair (s_lat, s_lon) of positive ints -> (s_lat, s_lon), or None for "no
+    stride" (None, 1, (1, 1): the unthinned decode).  Raises ValueError for anything that is not an integer (a float, a
+    bool, a string), for a value < 1, and for W % s_lon != 0: the thinned columns are those of the GLOBAL grid with
+    column % s_lon == 0, a lattice that closes round the circle only when s_lon divides W."""
+    if stride is None:
+        return None
+    parts = stride if isinstance(stride, (tuple, list, np.ndarray)) else (stride, stride)
+    try:
+        if len(parts) != 2 or any(isinstance(v, (bool, np.bool_)) for v in parts):
+            raise TypeError
+        sy, sx = (operator.index(v) for v in parts)
+    except TypeError:
+        raise ValueError(f"stride must be a positive int or a pair (s_lat, s_lon) of positive ints, got {stride!r}") from None
+    if sy < 1 or sx < 1:
+        raise ValueError(f"stride {stride!r}: strides must be >= 1")
+    if W % sx:
+        raise ValueError(f"stride {stride!r}: {W} % s_lon ({sx}) = {W % sx} != 0 - the thinned columns are the global "
+                         f"columns with column % s_lon == 0, which must close round the circle")
+    return None if (sy, sx) == (1, 1) else (sy, sx)
+
+
+def kept_points(box, stride, W=1440):
+    """The grid points of the box (r0, r1, c0, nc) that a stride (s_lat, s_lon) keeps -> (rows, cols), int64 arrays of
+    GLOBAL indices: the rows r of [r0, r1) with r % s_lat == 0, north to south, and the columns c of the box with
+    c % s_lon == 0, in the box's eastward order (wrapping at W).  The thinned grid is anchored to the global grid, not to
+    the box: a region's thinned decode is a sub-block of the globe's.  Raises ValueError when no row / column is kept."""
+    r0, r1, c0, nc = (int(v) for v in box)
+    sy, sx = (int(v) for v in stride)
+    rows = np.arange(-(-r0 // sy) * sy, r1, sy, dtype=np.int64)
+    cols = (c0 + np.arange(nc, dtype=np.int64)) % W
+    cols = cols[cols % sx == 0]
+    if not len(rows):
+        raise ValueError(f"stride {(sy, sx)!r}: the box rows [{r0}, {r1}) hold no row with row % {sy} == 0")
+    if not len(cols):
+        raise ValueError(f"stride {(sy, sx)!r}: the {nc} box columns from {c0} hold no column with column % {sx} == 0")
+    return rows, cols
+
+
+def grid_box(region, H=721, W=1440, stride=None):
     """region = (lat_min, lat_max, lon_min, lon_max) in degrees -> dict(rows=(r0, r1), col0, ncols, box, lat, lon).
 
     The box holds the grid points with lat in [lat_min, lat_max] and lon in the closed eastward interval from lon_min to
@@ -22,7 +64,11 @@ def grid_box(region, H=721, W=1440):
     360 deg or more is the whole circle - W columns, the first one at lon_min.  Rows run north to south (r1 exclusive),
     columns eastward from col0 (wrapping at W).  `box` = (r0, r1, col0, ncols) is what VAEformer.decompress /
     decode_latent take; lat / lon (float64, lon in [0, 360)) are the coordinates of the rows / columns.
-    Raises ValueError for an empty box, a latitude outside [-90, 90] or lat_min > lat_max."""
+    stride (resolve_stride): lat / lon are those of the kept rows / columns only (kept_points; `box` stays the unthinned
+    box) and the dict also carries stride = (s_lat, s_lon) and kept_rows / kept_cols (global indices).
+    Raises ValueError for an empty box, a latitude outside [-90, 90] or lat_min > lat_max, a bad stride, or a box in
+    which the stride keeps no row / no column."""
+    step = resolve_stride(stride, W)
     try:
         lat_min, lat_max, lon_min, lon_max = (float(v) for v in region)
     except (TypeError, ValueError):
@@ -52,8 +98,16 @@ def grid_box(region, H=721, W=1440):
     c0 = first % W
     rows = np.arange(r0, r_last + 1, dtype=np.float64)
     cols = (c0 + np.arange(nc)) % W
+    extra = {}
+    if step is not None:
+        try:
+            kr, cols = kept_points((r0, r_last + 1, c0, nc), step, W)
+        except ValueError as e:
+            raise ValueError(f"region {region!r}: {e}") from None
+        rows = kr.astype(np.float64)
+        extra = dict(stride=step, kept_rows=kr, kept_cols=cols)
     return dict(rows=(r0, r_last + 1), col0=c0, ncols=nc, box=(r0, r_last + 1, c0, nc),
-                lat=90.0 - rows * (180.0 / (H - 1)), lon=cols.astype(np.float64) * (360.0 / W))
+                lat=90.0 - rows * (180.0 / (H - 1)), lon=cols.astype(np.float64) * (360.0 / W), **extra)
 
 
 def resolve_variables(variables, vname_to_channels):
@@ -104,3 +158,127 @@ def token_plan(box, H, W, kh=11, kw=10, sh=10, sw=10):
     r_off, c_off = r0 - sh * ti0, (c0 - sw * tj0) % Ws
     return dict(ti0=ti0, n_ti=n_ti, tj0=tj0, n_tj=n_tj, Hs=Hs, Ws=Ws, r_off=r_off, c_off=c_off, Hb=r1 - r0, Wb=nc,
                 exact=(r_off == 0 and r1 - r0 == Hs and c_off == 0 and nc == Ws))
+
+
+def stride_plan(box, stride, H, W, kh=11, kw=10, sh=10, sw=10, C=1):
+    """The un-embed products a thinned box needs.  box = (r0, r1, c0, nc) | None (the globe); stride = (s_lat, s_lon)
+    (kept_points: anchored to the global grid; (1, 1) is allowed here and gives one class with every tap).
+
+    Token row ti writes image rows sh * ti + ky (ky < kh), so its kept taps are {ky : (sh * ti + ky) % s_lat == 0}; that
+    set depends on ti % P_r only (P_r = s_lat / gcd(sh, s_lat)): the token rows fall into at most P_r ROW CLASSES, the
+    token columns likewise into at most P_c = s_lon / gcd(sw, s_lon) COLUMN CLASSES of taps {kx : (sw * tj + kx) % s_lon
+    == 0} (W % s_lon == 0 makes the classes survive the wrap at the east edge).  A class pair (row class, column class)
+    is one small GEMM: its tokens x (channels x its ky taps x its kx taps).  Returns dict(
+      rows, cols: the kept global rows / columns (kept_points); Ho, Wo: their counts - the thinned image is [C, Ho, Wo];
+      row_classes: [dict(t0, step, n, taps, land)]: token rows t0, t0 + step, .. (n of them: those with a tap inside the
+        box - a kept seam row's partner outside the box's own token range included), taps = the class's ky, land int32
+        [n, len(taps)]: where (token row, ky) lands -  >= 0: that row of the thinned image (its only contribution);
+        -1: outside the box (computed, not used);  <= -2: seam slot -2 - (2 * s + slot) of seam s;
+      col_classes: the same along the columns (t0 + i * step mod Wp, eastward from the box's first token column; land
+        >= 0 | -1; kw == sw: no seams);
+      seams: int32 [n_seam], the thinned-image row of each kept seam row (image row sh * t, 0 < t < Hp: the sum of token
+        row t - 1 at ky = kh - 1 - slot 0, the UPPER partner, added first - and token row t at ky = 0 - slot 1);
+      needed_elems: C x the (token, tap) products that land in the thinned box (a seam row counts twice);
+      gemm_elems: the sum of M x N over the class GEMMs (M = n_ti * n_tj tokens, N = C * n_ky * n_kx columns; the GEMM
+        launchers bound-check their edge tiles and need no padded operand or output, so this is what is computed))."""
+    if kh != sh + 1 or kw != sw:
+        raise ValueError("subset decode needs the ERA5 un-embed geometry (kh = sh + 1, kw = sw)")
+    Hp, Wp = (H - kh) // sh + 1, (W - kw) // sw + 1
+    r0, r1, c0, nc = (0, H, 0, W) if box is None else (int(v) for v in box)
+    if not (0 <= r0 < r1 <= H and 0 <= c0 < W and 1 <= nc <= W):
+        raise ValueError(f"box {box!r}: need 0 <= r0 < r1 <= {H}, 0 <= c0 < {W}, 1 <= nc <= {W}")
+    sy, sx = (int(v) for v in stride)
+    if sy < 1 or sx < 1 or W % sx:
+        raise ValueError(f"stride {stride!r}: need s_lat >= 1, s_lon >= 1 and {W} % s_lon == 0")
+    rows, cols = kept_points((r0, r1, c0, nc), (sy, sx), W)
+    Ho, Wo = len(rows), len(cols)
+    out_row = np.full(H, -1, dtype=np.int64)
+    out_row[rows] = np.arange(Ho)
+    out_col = np.full(W, -1, dtype=np.int64)
+    out_col[cols] = np.arange(Wo)
+    seam_rows = [int(r) for r in rows if r % sh == 0 and 0 < r < H - 1]
+    seam_of = {r: s for s, r in enumerate(seam_rows)}
+
+    row_classes = []
+    Pr = sy // math.gcd(sh, sy)
+    for k in range(Pr):
+        taps = tuple(ky for ky in range(kh) if (sh * k + ky) % sy == 0)
+        tis = [ti for ti in range(k, Hp, Pr) if any(r0 <= sh * ti + ky < r1 for ky in taps)]
+        if not taps or not tis:
+            continue
+        land = np.full((len(tis), len(taps)), -1, dtype=np.int32)
+        for i, ti in enumerate(tis):
+            for a, ky in enumerate(taps):
+                r = sh * ti + ky
+                if not r0 <= r < r1:
+                    continue
+                if r in seam_of:     # ky == kh - 1: this token row is the one above the seam (upper, slot 0)
+                    land[i, a] = -2 - (2 * seam_of[r] + (0 if ky == kh - 1 else 1))
+                else:
+                    land[i, a] = out_row[r]
+        assert tis == list(range(tis[0], tis[0] + Pr * len(tis), Pr))
+        row_classes.append(dict(t0=tis[0], step=Pr, n=len(tis), taps=taps, land=land))
+
+    col_classes = []
+    Pc = sx // math.gcd(sw, sx)
+    u0 = c0 // sw
+    for k in range(Pc):
+        taps = tuple(kx for kx in range(kw) if (sw * k + kx) % sx == 0)
+        qs = [q for q in range(Wp) if (u0 + q) % Wp % Pc == k
+              and any(out_col[sw * ((u0 + q) % Wp) + kx] >= 0 for kx in taps)]
+        if not taps or not qs:
+            continue
+        assert qs == list(range(qs[0], qs[0] + Pc * len(qs), Pc))
+        tjs = [(u0 + q) % Wp for q in qs]
+        land = np.array([[out_col[sw * tj + kx] for kx in taps] for tj in tjs], dtype=np.int32)
+        col_classes.append(dict(t0=tjs[0], step=Pc, n=len(tjs), taps=taps, land=land))
+
+    n_r = sum(int((rc["land"] != -1).sum()) for rc in row_classes)
+    n_c = sum(int((cc["land"] != -1).sum()) for cc in col_classes)
+    gemm = sum(rc["n"] * cc["n"] * C * len(rc["taps"]) * len(cc["taps"]) for rc in row_classes for cc in col_classes)
+    return dict(rows=rows, cols=cols, Ho=Ho, Wo=Wo, row_classes=row_classes, col_classes=col_classes,
+                seams=np.array([out_row[r] for r in seam_rows], dtype=np.int32), needed_elems=C * n_r * n_c,
+                gemm_elems=gemm)
+
+
+SCATTER_ALIGN = 64      # class matrices start at multiples of this many floats in the workspace (256 bytes)
+
+
+def scatter_tables(plan, C):
+    """The lookup tables of ops.strided_scatter (cra5_strided_scatter_f32) for a stride_plan and C channels.  The class
+    matrices G[rc][cc] = [n_ti * n_tj tokens, C * n_ky * n_kx columns (c, ky, kx)] lie in ONE fp32 workspace; -> dict(
+      rows int32 [Ho, 6]: per thinned row its contributions (row class, token-row index, ky index) x 2 - a seam row has
+        two, UPPER first; every other row one, the second triple is (-1, 0, 0);
+      cols int32 [Wo, 3]: per thinned column (column class, token-column index, kx index);
+      cls int64 [n_rc * n_cc, 5]: per class pair (element offset of its matrix in the workspace, row pitch, n_tj, n_kx,
+        n_ky * n_kx);
+      n_cc, elems: workspace size in floats;  gemms: [(rc, cc, offset, M, N)] in launch order)."""
+    rcs, ccs = plan["row_classes"], plan["col_classes"]
+    Ho, Wo = plan["Ho"], plan["Wo"]
+    rows = np.zeros((Ho, 6), dtype=np.int32)
+    rows[:, 0] = rows[:, 3] = -1
+    for k, rc in enumerate(rcs):
+        for (i, a), v in np.ndenumerate(rc["land"]):
+            if v >= 0:
+                rows[v, 0:3] = (k, i, a)
+            elif v <= -2:
+                s, slot = divmod(-2 - int(v), 2)
+                rows[plan["seams"][s], 3 * slot:3 * slot + 3] = (k, i, a)
+    cols = np.full((Wo, 3), -1, dtype=np.int32)
+    for k, cc in enumerate(ccs):
+        for (i, a), v in np.ndenumerate(cc["land"]):
+            if v >= 0:
+                cols[v] = (k, i, a)
+    seam = np.zeros(Ho, dtype=bool)
+    seam[plan["seams"]] = True
+    if (rows[:, 0] < 0).any() or (cols[:, 0] < 0).any() or ((rows[:, 3] >= 0) != seam).any():
+        raise AssertionError("stride plan: a kept row / column has no source, or a seam row lacks a partner")
+    cls = np.zeros((len(rcs) * len(ccs), 5), dtype=np.int64)
+    gemms, off = [], 0
+    for i, rc in enumerate(rcs):
+        for j, cc in enumerate(ccs):
+            M, N = rc["n"] * cc["n"], C * len(rc["taps"]) * len(cc["taps"])
+            cls[i * len(ccs) + j] = (off, N, cc["n"], len(cc["taps"]), len(rc["taps"]) * len(cc["taps"]))
+            gemms.append((i, j, off, M, N))
+            off += -(-M * N // SCATTER_ALIGN) * SCATTER_ALIGN
+    return dict(rows=rows, cols=cols, cls=cls, n_cc=len(ccs), elems=off, gemms=gemms)

@@ -315,7 +315,8 @@ class VAEformer(nn.Module):
         # results); "split" keeps the hi planes of split rows (rounds 1-4; a test flips the attribute)
         self.f16_layout = "plain"
         self._derived = {}
-        # subset decode: un-embed weight rows / mean / std of chosen channel tuples, least recently used first, at most
+        # subset decode: un-embed weight rows / mean / std of chosen channel tuples (and a thinned decode's plan tables and
+        # per-class weight rows: one entry each per request shape), least recently used first, at most
         # SUBSET_CACHE entries (a long run over many different subsets does not grow device memory)
         self._sub_cache = OrderedDict()
         self._derive_lock = threading.RLock()
@@ -787,9 +788,10 @@ class VAEformer(nn.Module):
         return params[:L], params[L:]
 
     # ---- g_s --------------------------------------------------------------------------------
-    def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None):
-        """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300).  channels / box (canonical, _subset_args): the
-        [len(channels), r1 - r0, nc] slice of that frame, bit for bit (_unembed)."""
+    def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None, step=None):
+        """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300).  channels / box / step (canonical, _subset_args):
+        the [len(channels), r1 - r0, nc] slice of that frame - thinned to the global rows % s_lat == 0 / columns % s_lon
+        == 0 when step = (s_lat, s_lon) -, bit for bit (_unembed)."""
         cfg = self.cfg
         D, L = cfg['embed_dim'], cfg['latent_dim']
         N = self.Hp * self.Wp
@@ -803,7 +805,7 @@ class VAEformer(nn.Module):
         Cout, (Himg, Wimg) = cfg['out_chans'], cfg['img_size']
         # the LayerNorm writes plain rows when the whole frame's un-embed would take them (a subset's geometry may not)
         h = self._ln(t, self.g_s.norm, f"h{D}", plain=self._fused_unembed_form(Cout, Himg, Wimg)[1])
-        return self._unembed(h, mean, std, channels, box)
+        return self._unembed(h, mean, std, channels, box, step)
 
     # ---- un-embed: the whole frame, or chosen channels and / or a lat-lon box of it ---------------------------
     # The transformer runs on the whole grid (global attention); everything after the final LayerNorm is local.  The
@@ -835,6 +837,16 @@ class VAEformer(nn.Module):
             if box == (0, H, 0, W):
                 box = None
         return channels, box
+
+    def _step_arg(self, step, box):
+        """Validate a stride (int | (s_lat, s_lon) | None) for the canonical `box` of _subset_args -> (s_lat, s_lon), or
+        None for no thinning (None, 1, (1, 1): the unthinned path, unchanged).  ValueError for a bad stride
+        (subset.resolve_stride) or a box in which it keeps no row / no column."""
+        H, W = self.cfg['img_size']
+        step = subset.resolve_stride(step, W)
+        if step is not None:
+            subset.kept_points(box if box is not None else (0, H, 0, W), step, W)
+        return step
 
     def _sub_cached(self, key, src, make):
         """Entry `key` of the bounded subset cache, rebuilt by `make()` when `src` (the tensor / derived weight it was
@@ -885,10 +897,13 @@ class VAEformer(nn.Module):
                  if self.gemm_mode == "split" and self.fused_unembed and D <= 8192 else 0)
         return nside, bool(nside) and self._hi("g_s.final") and self.f16_layout == "plain" and D % 64 == 0
 
-    def _unembed(self, h, mean, std, chans, box):
+    def _unembed(self, h, mean, std, chans, box, step=None):
         """The un-embed for channels `chans` (tuple | None: all) inside grid box `box` (tuple | None: the whole grid),
         from the final LayerNorm's output h (SplitMat, or fp32 [N, D] on the exact-f32 engines) -> a fresh [C', Hb, Wb].
-        chans = box = None is the full decode."""
+        chans = box = None is the full decode.  step = (s_lat, s_lon): only the box's points on the global lattice
+        rows % s_lat == 0, columns % s_lon == 0 -> [C', Ho, Wo] (_unembed_thinned: the same products, far fewer)."""
+        if step is not None:
+            return self._unembed_thinned(h, mean, std, chans, box, step)
         cfg = self.cfg
         D = cfg['embed_dim']
         kh, kw = cfg['patch_size']
@@ -943,6 +958,85 @@ class VAEformer(nn.Module):
         if not p["exact"]:
             ops.crop(sup, p["r_off"], p["Hb"], p["c_off"], p["Wb"], out=out)
         return out
+
+    def _unembed_thinned(self, h, mean, std, chans, box, step):
+        """_unembed with a stride.  The un-embed is linear and local: weight row (c, ky, kx) writes one pixel of one
+        patch, so a thinned grid needs only the taps (ky, kx) that land on it - and those depend on the token's position
+        modulo a small period (subset.stride_plan: row classes x column classes).  Per class pair: gather its token rows
+        verbatim, gather the chosen channels' weight rows of its taps from the cached copy of the WHOLE weight, run the
+        two-call form's GEMM into a small matrix - the same MFMA chain over K per product as the full decode's launch,
+        whatever the tile (the reduced-precision mode names the full launch's k-step form, CRA5_GEMM_WIDE_K) - then ONE
+        scatter assembles the thinned image: upper + lower partner on seam rows, then x * std + mean, the full decode's
+        order and arithmetic.  No buffer of the full image's or the full column matrix's size exists on this path."""
+        cfg = self.cfg
+        D = cfg['embed_dim']
+        kh, kw = cfg['patch_size']
+        sh, sw = cfg['patch_stride']
+        Cout, (Himg, Wimg) = cfg['out_chans'], cfg['img_size']
+        Hp, Wp = self.Hp, self.Wp
+        Cs = len(chans) if chans is not None else Cout
+        split = self.gemm_mode == "split"
+
+        def make_plan():
+            p = subset.stride_plan(box, step, Himg, Wimg, kh, kw, sh, sw, C=Cs)
+            tb = subset.scatter_tables(p, Cs)
+            dev = {k: torch.from_numpy(tb[k]).to(self.device) for k in ("rows", "cols", "cls")}
+            return p, tb, dev
+        # (`src` of the cache entry: the model itself - the geometry depends on no tensor, its device copy on the device)
+        p, tb, tdev = self._sub_cached(("plan", self.device, box, step, Cs), self, make_plan)
+        rcs, ccs = p["row_classes"], p["col_classes"]
+        ms, ss = self._stats_of_channels(mean, chans), self._stats_of_channels(std, chans)
+        key, w = "g_s.final", self.g_s.final.weight
+        Mf, Nf = Hp * Wp, Cout * kh * kw
+        hi = wide = False
+        if split:
+            # the weight copy and k-step form of the full decode's launch (fused pair or two-call form, _unembed)
+            wsp = self._wsplit(key, w)
+            hi = self._hi(key)
+            if self._fused_unembed_form(Cout, Himg, Wimg)[0]:
+                kind, wide = ("plain" if h.plain else "split"), hi and wsp.Kp % 64 == 0
+            else:
+                kind, wide = ("plain" if self._plain_gemm(key, Mf, Nf, wsp.K) else "split"), hi and ops.plain_ok(Mf, Nf, wsp.Kp)
+            wfull = self._wplain(key, w) if kind == "plain" else wsp
+        else:
+            kind, wfull = "f32", self._wf32(key, w)
+        taps = (tuple(rc["taps"] for rc in rcs), tuple(cc["taps"] for cc in ccs))
+        cch = chans if chans is not None else range(Cout)
+
+        def make_weights():
+            ws = {}
+            for i, rc in enumerate(rcs):
+                for j, cc in enumerate(ccs):
+                    idx = torch.tensor([(c * kh + ky) * kw + kx for c in cch for ky in rc["taps"] for kx in cc["taps"]],
+                                       device=self.device, dtype=torch.long)
+                    if split:
+                        ws[i, j] = ops.SplitMat(wfull.data.index_select(0, idx), len(idx), wfull.K, wfull.Kp,
+                                                wfull.scale_inv, plain=wfull.plain)
+                    else:
+                        ws[i, j] = wfull.index_select(0, idx)
+            return ws
+        wcls = self._sub_cached(("wtaps", kind, chans, taps), wfull, make_weights)
+        # A operands: each token belongs to one class (at most), so the classes' rows fit one [tokens, D] workspace
+        n_tok = sum(M for _, _, _, M, _ in tb["gemms"])
+        a_all = self._sbuf("ue_a_thin", n_tok, D) if split else self._buf("ue_a_thin", (n_tok, D))
+        g = self._buf("ue_g_thin", (tb["elems"],))
+        row0 = 0
+        for i, j, off, M, N in tb["gemms"]:
+            rc, cc = rcs[i], ccs[j]
+            if split:
+                dst = ops.SplitMat(a_all.data[row0:row0 + M], M, h.K, h.Kp)
+            else:
+                dst = a_all[row0:row0 + M]
+            a = ops.gather_token_rows(h, dst, Hp, Wp, rc["t0"], rc["n"], cc["t0"], cc["n"], ti_step=rc["step"],
+                                      tj_step=cc["step"])
+            gc = g[off:off + M * N].view(M, N)
+            if split:
+                ops.gemm_nt_split(a, wcls[i, j], out=gc, hi_only=hi, wide_k=wide)
+            else:
+                ops.gemm_nt(a, wcls[i, j], out=gc)
+            row0 += M
+        out = torch.empty((Cs, p["Ho"], p["Wo"]), device=self.device, dtype=torch.float32)
+        return ops.strided_scatter(g, tdev["rows"], tdev["cols"], tdev["cls"], tb["n_cc"], Cs, mean=ms, std=ss, out=out)
 
     # ---- latent side: everything between y and the entropy coder ---------------------------
     def _latent_side_frame(self, y, want_lik=False, z_sym_out=None):
@@ -1056,25 +1150,26 @@ class VAEformer(nn.Module):
             return y, self._finite(flag), None
         return self._range_guard(0, run, "encode")
 
-    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None):
+    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None):
         """g_s of one frame inside the caller's GPU phase -> (x_hat, pinned probe values: test them with _finite once
         the phase has ended).  The residual stream after the last block carries every upstream poison - token-wise, and
         the global attention spreads it.  The final LayerNorm's split store is O(gamma * sqrt(D)): a checkpoint with
         |gamma| sqrt(D) >= 65 504, or a non-finite mean / std, poisons x_hat BEHIND that probe - a strided sample of the
         reconstruction itself (every 2053rd pixel: ~14 samples of each token's 268 x 110-pixel patch, ~500 of every
-        channel) is probed as well.  A subset decode (channels / box) probes the decoded subset itself: every
-        output channel sampled at least min(its element count, 500) times."""
-        x_hat = self._decode_frame(y_hat, mean=mean, std=std, channels=channels, box=box)
+        channel) is probed as well.  A subset decode (channels / box / step) probes the decoded subset itself:
+        every output channel sampled at least min(its element count, 500) times."""
+        x_hat = self._decode_frame(y_hat, mean=mean, std=std, channels=channels, box=box, step=step)
         D = self.cfg['embed_dim']
-        stride = 2053 if channels is None and box is None else max(1, (x_hat.numel() // x_hat.shape[0]) // 500)
+        whole = channels is None and box is None and step is None
+        stride = 2053 if whole else max(1, (x_hat.numel() // x_hat.shape[0]) // 500)
         return x_hat, self._to_host("ok1", self._probe(self._buf(f"t{D}", (self.Hp * self.Wp, D)), (x_hat, stride)))
 
-    def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None):
+    def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None, step=None):
         """g_s of one frame under the range guard: y_hat [L, Hp, Wp] -> x_hat [C, H, W] (or its subset: canonical
-        channels / box of _subset_args)."""
+        channels / box of _subset_args, step of _step_arg)."""
         def run():
             with self._gpu_phase():
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, run, "decode")
 
@@ -1105,13 +1200,17 @@ class VAEformer(nn.Module):
         return y, None, None
 
     @torch.no_grad()
-    def decode_latent(self, y, type='quantized', channels=None, box=None):
+    def decode_latent(self, y, type='quantized', channels=None, box=None, step=None):
         """vaeformer.py:294-300.  channels: output channel indices (in the order given); box = (r0, r1, c0, nc): grid rows
         [r0, r1) and nc columns from c0, wrapping at W (subset.grid_box) -> [B, len(channels), r1 - r0, nc], the same
-        slice of the full decode bit for bit."""
+        slice of the full decode bit for bit.  step: a stride, int | (s_lat, s_lon) - of the box (default: the globe) only
+        the rows r with r % s_lat == 0 and the columns c with c % s_lon == 0 (GLOBAL indices; subset.kept_points), again
+        bit for bit: with `full` the full decode under the same engines and precision, the result equals
+        full[channels][:, kept_rows][:, :, kept_cols] as bit patterns.  None / 1 / (1, 1): no thinning."""
         self._require_gpu()
         channels, box = self._subset_args(channels, box)
-        return torch.stack([self._decode_guarded(y[b], channels=channels, box=box) for b in range(y.shape[0])])
+        step = self._step_arg(step, box)
+        return torch.stack([self._decode_guarded(y[b], channels=channels, box=box, step=step) for b in range(y.shape[0])])
 
     @torch.no_grad()
     def forward(self, x):
@@ -1248,9 +1347,10 @@ class VAEformer(nn.Module):
             "(a .bin written by the PyTorch reference or by another engine; DESIGN.md section 2).  A damaged y "
             "stream or a different checkpoint looks the same.  Nothing was reconstructed", e.status)
 
-    def _decompress_frame(self, y_string, z_string, shape, reconstruct, mean=None, std=None, channels=None, box=None):
+    def _decompress_frame(self, y_string, z_string, shape, reconstruct, mean=None, std=None, channels=None, box=None,
+                          step=None):
         """host: decode z | GPU: h_s, indexes | host: decode y | GPU: de-quantise (+ g_s: the whole frame, or the
-        canonical channels / box of _subset_args)."""
+        canonical channels / box of _subset_args, step of _step_arg)."""
         eb, gc = self.entropy_bottleneck, self.gaussian_conditional
         Cz = eb.channels
         zh, zw = int(shape[0]), int(shape[1])
@@ -1325,23 +1425,25 @@ class VAEformer(nn.Module):
                     y_hat = ops.gaussian_conditional(scales, means, gc.scale_table, sym_in=y_sym, want=("y_hat",))["y_hat"]
                 if not reconstruct:
                     return y_hat, True, None
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, gpu_side, "decompress")
 
     @torch.no_grad()
-    def decompress(self, strings, shape, return_format='reconstructed', channels=None, box=None):
-        """vaeformer.py:378-400.  channels / box: a subset of the reconstruction (decode_latent)."""
+    def decompress(self, strings, shape, return_format='reconstructed', channels=None, box=None, step=None):
+        """vaeformer.py:378-400.  channels / box / step: a subset of the reconstruction (decode_latent)."""
         self._require_gpu()
         assert isinstance(strings, list) and len(strings) == 2
         rec = return_format != 'latent'
-        if not rec and (channels is not None or box is not None):
-            raise ValueError("decompress: return_format='latent' returns the latent; channels / box select a subset "
-                             "of the reconstruction")
+        if not rec and (channels is not None or box is not None or step is not None):
+            raise ValueError("decompress: return_format='latent' returns the latent; channels / box / step select a "
+                             "subset of the reconstruction")
         channels, box = self._subset_args(channels, box)
+        step = self._step_arg(step, box)
         self.entropy_bottleneck._check()
         self.gaussian_conditional._check()
-        out = torch.stack([self._decompress_frame(strings[0][b], strings[1][b], shape, rec, channels=channels, box=box)
+        out = torch.stack([self._decompress_frame(strings[0][b], strings[1][b], shape, rec, channels=channels, box=box,
+                                                  step=step)
                            for b in range(len(strings[0]))])
         if not rec:
             return out

@@ -281,6 +281,27 @@ int cra5_gather_token_rows(const void *src, size_t src_pitch_bytes, void *dst, s
                            size_t row_bytes, int Hp, int Wp, int ti0, int n_ti, int tj0, int n_tj, void *stream);
 int cra5_crop_f32(const float *src, int C, int Hs, int Ws, float *dst, int r0, int Hb, int c0, int Wb, void *stream);
 
+/* Thinned decode (csrc/subset.hip; cra5_amd/subset.py stride_plan / scatter_tables): every s_lat-th row and s_lon-th
+ * column of the global grid.  The tokens fall into classes that keep the same un-embed taps; each class pair is one small
+ * GEMM (cra5_gemm_nt_split / cra5_gemm_nt_f32) on the class's token rows and the chosen channels' rows of its taps.
+ * cra5_gather_token_lattice: cra5_gather_token_rows for a strided lattice - dst row r = i * n_tj + j <- src row
+ * (ti0 + i * ti_step) * Wp + (tj0 + j * tj_step) mod Wp; same alignment rules; 0 <= ti0, ti0 + (n_ti - 1) * ti_step < Hp,
+ * 0 <= tj0 < Wp, (n_tj - 1) * tj_step < Wp (one wrap at most, no token twice), steps >= 1 - CRA5_ERR_ARG otherwise.
+ * cra5_strided_scatter_f32: x[c][i][j] (contiguous [C][Ho][Wo]) from the class matrices that lie in the workspace g of
+ * g_elems floats.  Device tables: rows int32 [Ho][6] = (rc, ti, ky) of the row's first contribution and of its second
+ * (rc = -1: none) - a seam row (image row 10 t, 0 < t < Hp) is token row t - 1's last tap, the UPPER partner, first, plus
+ * token row t's tap 0; cols int32 [Wo][3] = (cc, tj, kx); cls int64 [n_rc * n_cc][5] = (offset, row pitch, n_tj, n_kx,
+ * n_ky * n_kx) of class (rc, cc), whose matrix element is g[offset + (ti * n_tj + tj) * pitch + c * n_ky * n_kx + ky * n_kx
+ * + kx] (ti, tj, ky, kx: indices within the class).  x = (first [+ second]) [* std[c] + mean[c] when mean != NULL] - the
+ * order and arithmetic of the full decode's stores.  An element outside [0, g_elems) is not read: the point becomes NaN.
+ * mean and std both NULL or both given; pointers aligned to their element size - CRA5_ERR_ARG otherwise. */
+int cra5_gather_token_lattice(const void *src, size_t src_pitch_bytes, void *dst, size_t dst_pitch_bytes,
+                              size_t row_bytes, int Hp, int Wp, int ti0, int ti_step, int n_ti, int tj0, int tj_step,
+                              int n_tj, void *stream);
+int cra5_strided_scatter_f32(const float *g, size_t g_elems, const int *rows, const int *cols, const long long *cls,
+                             int n_rc, int n_cc, const float *mean, const float *stdv, float *x, int C, int Ho, int Wo,
+                             void *stream);
+
 /* Finiteness probe of the range guard: partials[b] = sum of x[i * stride] over block b's share of i = 0 .. ceil(n / stride)
  * - 1, b = 0 .. CRA5_PROBE_PARTIALS - 1 (written, never accumulated: no memset, deterministic).  A partial is non-finite as
  * soon as one addend is; the caller copies the partials to the host with the phase's other results and tests them there. */
