@@ -260,6 +260,16 @@ class SplitMat:
         data = (torch.zeros if zero else torch.empty)((rows, 2 * Kp), device=device, dtype=torch.int16)
         return SplitMat(data, rows, K, Kp)
 
+    def planes(self):
+        """The stored halves as two fp32 [rows, K] tensors (hi, lo), NOT multiplied by scale_inv (tests: the operands the
+        MFMAs really read).  A plain matrix has no lo plane: zeros."""
+        if self.plain:
+            hi = self.data.view(torch.float16)[:, : self.K].float()
+            return hi, torch.zeros_like(hi)
+        h = self.data.view(torch.float16).view(self.rows, self.Kp // 32, 2, 32).float()
+        return (h[:, :, 0].reshape(self.rows, self.Kp)[:, : self.K].contiguous(),
+                h[:, :, 1].reshape(self.rows, self.Kp)[:, : self.K].contiguous())
+
     def to_float(self):
         """Reconstruct the fp32 values (tests / debugging)."""
         if self.plain:
