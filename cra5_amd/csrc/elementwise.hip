@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void col2im_kernel(const float *__restrict__ c
 // ---------------------------------------------------------------------------------------
 // LDS-tiled patch gather / overlap-add for the ERA5 geometry (kw == sw: patches do not overlap
 // along W; kh = sh + 1: one shared row between vertically adjacent patches).
-// One block = (patch row ph, 16 consecutive patches, 8 channels): the 8 x kh image-row segments
+// One block step = (patch row ph, 16 consecutive patches, TILE_CH channels): the TILE_CH x kh image-row segments
 // of 16*kw floats (640-byte coalesced runs) are staged once in LDS; every output token then
 // writes 8*kh*kw consecutive K entries (3.5 KB runs).  HBM-bound: 1.11 GB in, 1.22 GB out.
 // ---------------------------------------------------------------------------------------
@@ -169,6 +169,10 @@ constexpr int TILE_TOK = 16;
 // even: the K offset c0*KH*KW of a block has to be a multiple of 4 floats for the 16-byte accesses.
 constexpr int TILE_CH = 2;      // gather (im2col)
 constexpr int TILE_CH_S = 2;    // scatter (col2im)
+// channel chunks a gather block walks, the next chunk's image rows in flight (registers) while this one is emitted.
+// Measured at 268 x 721 x 1440 against one chunk per block (three interleaved rounds, medians of 40 launches): plain rows
+// 466 -> 424 us at 2, 427 at 4, 437 at 8, 443 at 16; split rows (store-bound: twice the bytes written) 538 -> 531 at 2-8, 547 at 16.
+constexpr int IM2COL_GROUP = 2;
 
 // LDS image of both kernels: token-major [16 tokens][8*KH*KW (+4 pad)] = the GEMM-side layout,
 // so the GEMM-side accesses are contiguous ds_read/write_b128 + 16-byte global accesses, and the
@@ -181,53 +185,67 @@ __global__ __launch_bounds__(256) void im2col_tiled_kernel(const float *__restri
   constexpr int SEG = TILE_TOK * KW;             // floats per staged image-row segment
   constexpr int TS = TILE_CH * KH * KW + 4;      // LDS token stride (floats)
   static_assert((TILE_CH * KH * KW) % 4 == 0, "a block's K offset must stay 16-byte aligned");
+  // independent 16-byte loads in flight per thread: one channel chunk's image rows (880 pieces) in ONE pass of the block
+  constexpr int NL = 4;
+  static_assert(TILE_CH * KH * (SEG / 4) <= 256 * NL, "a channel chunk must fit one pass of loads");
   __shared__ __attribute__((aligned(16))) float tile[TILE_TOK * TS];
-  // block order: channel chunk fastest -> consecutive blocks sweep the K axis of the same 16
+  // block order: channel group fastest -> consecutive blocks sweep the K axis of the same 16
   // tokens (the 118 KB token rows of the column matrix are streamed front to back)
   const int tiles_w = Wp / TILE_TOK;
   const int n_cc = (C + TILE_CH - 1) / TILE_CH;
-  const int cc = blockIdx.x % n_cc;
-  const int pwt = (blockIdx.x / n_cc) % tiles_w;
-  const int ph = blockIdx.x / (n_cc * tiles_w);
-  const int c0 = cc * TILE_CH;
-  const int nc = min(TILE_CH, C - c0);
+  constexpr int G = IM2COL_GROUP;
+  const int n_g = (n_cc + G - 1) / G;
+  const int g = blockIdx.x % n_g;
+  const int pwt = (blockIdx.x / n_g) % tiles_w;
+  const int ph = blockIdx.x / (n_g * tiles_w);
   const int col0 = pwt * SEG;
-  // ---- stage: image rows (c, i) in 16-byte pieces -> tile[t][(c*KH + i)*KW + j] ------------------
-  const int n4 = nc * KH * (SEG / 4);
-  constexpr int UNR = 7;   // independent 16-byte loads in flight per thread (memory-level parallelism)
-  for (int e0 = threadIdx.x; e0 < n4; e0 += 256 * UNR) {
-    float4 v[UNR];
+  const int cc_lo = g * G, cc_hi = min(cc_lo + G, n_cc);
+  // A block walks G channel chunks.  The image rows of chunk cc + 1 are requested (NL loads per thread, into registers)
+  // right after chunk cc's LDS image is complete and stay in flight while chunk cc is emitted: the load side never
+  // drains between chunks, as in a streaming kernel.  The LDS image, the emit side and the arithmetic are per chunk
+  // what a block of one chunk does.
+  float4 v[NL];
+  auto load = [&](int cc) {
+    const int c0 = cc * TILE_CH;
+    const int n4 = min(TILE_CH, C - c0) * KH * (SEG / 4);
 #pragma unroll
-    for (int q = 0; q < UNR; ++q) {
-      const int e = min(e0 + q * 256, n4 - 1);
+    for (int q = 0; q < NL; ++q) {
+      const int e = min((int)threadIdx.x + q * 256, n4 - 1);
       const int row = e / (SEG / 4), p4 = e - row * (SEG / 4);
       const int c = row / KH, i = row - c * KH;
       v[q] = *reinterpret_cast<const float4 *>(x + ((size_t)(c0 + c) * H + (ph * sh + i)) * W + col0 + p4 * 4);
     }
+  };
+  load(cc_lo);
+  for (int cc = cc_lo; cc < cc_hi; ++cc) {
+  const int c0 = cc * TILE_CH;
+  const int nc = min(TILE_CH, C - c0);
+  // ---- stage: image rows (c, i) in 16-byte pieces -> tile[t][(c*KH + i)*KW + j] ------------------
+  const int n4 = nc * KH * (SEG / 4);
 #pragma unroll
-    for (int q = 0; q < UNR; ++q) {
-      const int e = e0 + q * 256;
-      if (e < n4) {
-        const int row = e / (SEG / 4), p4 = e - row * (SEG / 4);   // row = c*KH + i
-        const int c = row / KH;
-        float vv[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
-        if (mean) {
-          const float m = mean[c0 + c], sd = stdv[c0 + c];
+  for (int q = 0; q < NL; ++q) {
+    const int e = threadIdx.x + q * 256;
+    if (e < n4) {
+      const int row = e / (SEG / 4), p4 = e - row * (SEG / 4);   // row = c*KH + i
+      const int c = row / KH;
+      float vv[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+      if (mean) {
+        const float m = mean[c0 + c], sd = stdv[c0 + c];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) vv[u] = (vv[u] - m) / sd;
-        }
+        for (int u = 0; u < 4; ++u) vv[u] = (vv[u] - m) / sd;
+      }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int col = p4 * 4 + u;
-          const int t = col / KW, j = col - t * KW;
-          tile[t * TS + row * KW + j] = vv[u];
-        }
+      for (int u = 0; u < 4; ++u) {
+        const int col = p4 * 4 + u;
+        const int t = col / KW, j = col - t * KW;
+        tile[t * TS + row * KW + j] = vv[u];
       }
     }
   }
   __syncthreads();
+  if (cc + 1 < cc_hi) load(cc + 1);
   // ---- emit: contiguous K runs per token ----------------------------------------------------------
-  const int kpt = nc * KH * KW;                  // K entries per token in this block
+  const int kpt = nc * KH * KW;                  // K entries per token in this chunk
   const int q4 = (kpt + 3) / 4;
   const int kbase = c0 * KH * KW;                // multiple of 4 (TILE_CH * KH * KW = 220)
   for (int e = threadIdx.x; e < TILE_TOK * q4; e += 256) {
@@ -259,6 +277,8 @@ __global__ __launch_bounds__(256) void im2col_tiled_kernel(const float *__restri
       const int t = e / npad, k = K + (e - t * npad);
       cols_s[((size_t)ph * Wp + pwt * TILE_TOK + t) * 2 * ldk + k] = 0;
     }
+  }
+  if (cc + 1 < cc_hi) __syncthreads();   // the next chunk overwrites the LDS image
   }
 }
 
@@ -718,7 +738,8 @@ int cra5_im2col_f32(const float *x, const float *mean, const float *stdv, float 
   // ERA5 patch geometry: LDS-tiled streaming kernel
   if (kh == 11 && kw == 10 && sw == 10 && sh == 10 && Wp % TILE_TOK == 0 && (W % 4) == 0 && (ldk % 4) == 0 &&
       ((uintptr_t)x & 15) == 0) {
-    const int blocks = (Wp / TILE_TOK) * Hp * ((C + TILE_CH - 1) / TILE_CH);
+    const int n_cc = (C + TILE_CH - 1) / TILE_CH;
+    const int blocks = (Wp / TILE_TOK) * Hp * ((n_cc + IM2COL_GROUP - 1) / IM2COL_GROUP);
     hipLaunchKernelGGL((im2col_tiled_kernel<11, 10>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, mean, stdv,
                        cols, cols_split, C, H, W, sh, Hp, Wp, ldk, split_plain);
     return (int)hipGetLastError();

@@ -788,10 +788,11 @@ class VAEformer(nn.Module):
         return params[:L], params[L:]
 
     # ---- g_s --------------------------------------------------------------------------------
-    def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None, step=None):
+    def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None):
         """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300).  channels / box / step (canonical, _subset_args):
         the [len(channels), r1 - r0, nc] slice of that frame - thinned to the global rows % s_lat == 0 / columns % s_lon
-        == 0 when step = (s_lat, s_lon) -, bit for bit (_unembed)."""
+        == 0 when step = (s_lat, s_lon) -, bit for bit (_unembed).  out: the contiguous destination of _decoded_shape
+        (one frame of the caller's batch result) - the un-embed writes x_hat there; None: a fresh tensor."""
         cfg = self.cfg
         D, L = cfg['embed_dim'], cfg['latent_dim']
         N = self.Hp * self.Wp
@@ -805,7 +806,7 @@ class VAEformer(nn.Module):
         Cout, (Himg, Wimg) = cfg['out_chans'], cfg['img_size']
         # the LayerNorm writes plain rows when the whole frame's un-embed would take them (a subset's geometry may not)
         h = self._ln(t, self.g_s.norm, f"h{D}", plain=self._fused_unembed_form(Cout, Himg, Wimg)[1])
-        return self._unembed(h, mean, std, channels, box, step)
+        return self._unembed(h, mean, std, channels, box, step, out)
 
     # ---- un-embed: the whole frame, or chosen channels and / or a lat-lon box of it ---------------------------
     # The transformer runs on the whole grid (global attention); everything after the final LayerNorm is local.  The
@@ -885,6 +886,27 @@ class VAEformer(nn.Module):
         return self._sub_cached(("stat", t.data_ptr(), t._version, chans), t,
                                 lambda: t.index_select(0, torch.tensor(chans, device=t.device, dtype=torch.long)))
 
+    def _decoded_shape(self, channels=None, box=None, step=None):
+        """[C', H', W'] of one decoded frame for the canonical channels / box (_subset_args) and step (_step_arg)."""
+        H, W = self.cfg['img_size']
+        C = len(channels) if channels is not None else self.cfg['out_chans']
+        r0, r1, _, nc = box if box is not None else (0, H, 0, W)
+        if step is None:
+            return C, r1 - r0, nc
+        rows, cols = subset.kept_points(box if box is not None else (0, H, 0, W), step, W)
+        return C, len(rows), len(cols)
+
+    def _frame_dest(self, out, shape):
+        """The destination of one frame's un-embed: the caller's `out` (a frame of a batch result: checked), or a fresh
+        tensor - never a per-thread workspace, the result outlives the call."""
+        if out is None:
+            return torch.empty(shape, device=self.device, dtype=torch.float32)
+        if not (tuple(out.shape) == tuple(shape) and out.dtype == torch.float32 and out.device == self.device
+                and out.is_contiguous()):
+            raise ValueError(f"decode destination: need a contiguous fp32 {tuple(shape)} tensor on {self.device}, got "
+                             f"{tuple(out.shape)} {out.dtype} on {out.device}")
+        return out
+
     def _fused_unembed_form(self, C, H, W):
         """The un-embed of a [C, H, W] image: -> (nside, plain).  nside > 0: ONE fused launch pair runs - the GEMM
         epilogue scatters into the image (de-normalised), the overlap rows go through a side buffer of nside bytes (no
@@ -897,13 +919,15 @@ class VAEformer(nn.Module):
                  if self.gemm_mode == "split" and self.fused_unembed and D <= 8192 else 0)
         return nside, bool(nside) and self._hi("g_s.final") and self.f16_layout == "plain" and D % 64 == 0
 
-    def _unembed(self, h, mean, std, chans, box, step=None):
+    def _unembed(self, h, mean, std, chans, box, step=None, out=None):
         """The un-embed for channels `chans` (tuple | None: all) inside grid box `box` (tuple | None: the whole grid),
-        from the final LayerNorm's output h (SplitMat, or fp32 [N, D] on the exact-f32 engines) -> a fresh [C', Hb, Wb].
-        chans = box = None is the full decode.  step = (s_lat, s_lon): only the box's points on the global lattice
-        rows % s_lat == 0, columns % s_lon == 0 -> [C', Ho, Wo] (_unembed_thinned: the same products, far fewer)."""
+        from the final LayerNorm's output h (SplitMat, or fp32 [N, D] on the exact-f32 engines) -> [C', Hb, Wb], written
+        into `out` (_frame_dest: a frame of the caller's batch result - every form below stores straight into it; None:
+        a fresh tensor).  chans = box = None is the full decode.  step = (s_lat, s_lon): only the box's points on the
+        global lattice rows % s_lat == 0, columns % s_lon == 0 -> [C', Ho, Wo] (_unembed_thinned: the same products, far
+        fewer)."""
         if step is not None:
-            return self._unembed_thinned(h, mean, std, chans, box, step)
+            return self._unembed_thinned(h, mean, std, chans, box, step, out)
         cfg = self.cfg
         D = cfg['embed_dim']
         kh, kw = cfg['patch_size']
@@ -927,7 +951,7 @@ class VAEformer(nn.Module):
             dst = self._sbuf("ue_a_sub", M, D) if split else self._buf("ue_a_sub", (M, D))
             a = ops.gather_token_rows(h, dst, Hp, Wp, p["ti0"], p["n_ti"], p["tj0"], p["n_tj"])
         Hs, Ws = p["Hs"], p["Ws"]
-        out = torch.empty((Cs, p["Hb"], p["Wb"]), device=self.device, dtype=torch.float32)
+        out = self._frame_dest(out, (Cs, p["Hb"], p["Wb"]))
         sup = out if p["exact"] else self._buf("ue_sup", (Cs, Hs, Ws))
         key, w = "g_s.final", self.g_s.final.weight
         nside = self._fused_unembed_form(Cs, Hs, Ws)[0]
@@ -959,7 +983,7 @@ class VAEformer(nn.Module):
             ops.crop(sup, p["r_off"], p["Hb"], p["c_off"], p["Wb"], out=out)
         return out
 
-    def _unembed_thinned(self, h, mean, std, chans, box, step):
+    def _unembed_thinned(self, h, mean, std, chans, box, step, out=None):
         """_unembed with a stride.  The un-embed is linear and local: weight row (c, ky, kx) writes one pixel of one
         patch, so a thinned grid needs only the taps (ky, kx) that land on it - and those depend on the token's position
         modulo a small period (subset.stride_plan: row classes x column classes).  Per class pair: gather its token rows
@@ -1035,7 +1059,7 @@ class VAEformer(nn.Module):
             else:
                 ops.gemm_nt(a, wcls[i, j], out=gc)
             row0 += M
-        out = torch.empty((Cs, p["Ho"], p["Wo"]), device=self.device, dtype=torch.float32)
+        out = self._frame_dest(out, (Cs, p["Ho"], p["Wo"]))
         return ops.strided_scatter(g, tdev["rows"], tdev["cols"], tdev["cls"], tb["n_cc"], Cs, mean=ms, std=ss, out=out)
 
     # ---- latent side: everything between y and the entropy coder ---------------------------
@@ -1150,26 +1174,28 @@ class VAEformer(nn.Module):
             return y, self._finite(flag), None
         return self._range_guard(0, run, "encode")
 
-    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None):
+    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None, out=None):
         """g_s of one frame inside the caller's GPU phase -> (x_hat, pinned probe values: test them with _finite once
         the phase has ended).  The residual stream after the last block carries every upstream poison - token-wise, and
         the global attention spreads it.  The final LayerNorm's split store is O(gamma * sqrt(D)): a checkpoint with
         |gamma| sqrt(D) >= 65 504, or a non-finite mean / std, poisons x_hat BEHIND that probe - a strided sample of the
         reconstruction itself (every 2053rd pixel: ~14 samples of each token's 268 x 110-pixel patch, ~500 of every
         channel) is probed as well.  A subset decode (channels / box / step) probes the decoded subset itself:
-        every output channel sampled at least min(its element count, 500) times."""
-        x_hat = self._decode_frame(y_hat, mean=mean, std=std, channels=channels, box=box, step=step)
+        every output channel sampled at least min(its element count, 500) times.  out: _decode_frame's destination -
+        the probe reads the frame where it was written."""
+        x_hat = self._decode_frame(y_hat, mean=mean, std=std, channels=channels, box=box, step=step, out=out)
         D = self.cfg['embed_dim']
         whole = channels is None and box is None and step is None
         stride = 2053 if whole else max(1, (x_hat.numel() // x_hat.shape[0]) // 500)
         return x_hat, self._to_host("ok1", self._probe(self._buf(f"t{D}", (self.Hp * self.Wp, D)), (x_hat, stride)))
 
-    def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None, step=None):
+    def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None):
         """g_s of one frame under the range guard: y_hat [L, Hp, Wp] -> x_hat [C, H, W] (or its subset: canonical
-        channels / box of _subset_args, step of _step_arg)."""
+        channels / box of _subset_args, step of _step_arg).  out: the frame's destination (_decode_frame); a re-run on
+        the exact-f32 engines overwrites the same destination."""
         def run():
             with self._gpu_phase():
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, run, "decode")
 
@@ -1210,21 +1236,26 @@ class VAEformer(nn.Module):
         self._require_gpu()
         channels, box = self._subset_args(channels, box)
         step = self._step_arg(step, box)
-        return torch.stack([self._decode_guarded(y[b], channels=channels, box=box, step=step) for b in range(y.shape[0])])
+        # the batch result is allocated once and every frame's un-embed stores into its slice (no stack copy)
+        out = torch.empty((y.shape[0],) + self._decoded_shape(channels, box, step), device=self.device, dtype=torch.float32)
+        for b in range(y.shape[0]):
+            self._decode_guarded(y[b], channels=channels, box=box, step=step, out=out[b])
+        return out
 
     @torch.no_grad()
     def forward(self, x):
         """vaeformer.py:302-333."""
         self._require_gpu()
-        xh, yl, zl, ys = [], [], [], []
+        yl, zl, ys = [], [], []
+        xh = torch.empty((x.shape[0],) + self._decoded_shape(), device=self.device, dtype=torch.float32)
         for b in range(x.shape[0]):
             y = self._encode_y_guarded(x[b])
             s = self._latent_side_guarded(y, want_lik=True)
-            xh.append(self._decode_guarded(s["y_hat"].reshape(y.shape)))
+            self._decode_guarded(s["y_hat"].reshape(y.shape), out=xh[b])
             yl.append(s["y_lik"].reshape(y.shape))
             zl.append(s["z_lik"].reshape(-1, self.Hz, self.Wz))
             ys.append(y)
-        return {"x_hat": torch.stack(xh), "likelihoods": {"y": torch.stack(yl), "z": torch.stack(zl)},
+        return {"x_hat": xh, "likelihoods": {"y": torch.stack(yl), "z": torch.stack(zl)},
                 "posterior": _Posterior(torch.stack(ys))}
 
     def _z_pool(self):
@@ -1348,9 +1379,10 @@ class VAEformer(nn.Module):
             "stream or a different checkpoint looks the same.  Nothing was reconstructed", e.status)
 
     def _decompress_frame(self, y_string, z_string, shape, reconstruct, mean=None, std=None, channels=None, box=None,
-                          step=None):
+                          step=None, out=None):
         """host: decode z | GPU: h_s, indexes | host: decode y | GPU: de-quantise (+ g_s: the whole frame, or the
-        canonical channels / box of _subset_args, step of _step_arg)."""
+        canonical channels / box of _subset_args, step of _step_arg; out: the reconstruction's destination,
+        _decode_frame)."""
         eb, gc = self.entropy_bottleneck, self.gaussian_conditional
         Cz = eb.channels
         zh, zw = int(shape[0]), int(shape[1])
@@ -1425,7 +1457,7 @@ class VAEformer(nn.Module):
                     y_hat = ops.gaussian_conditional(scales, means, gc.scale_table, sym_in=y_sym, want=("y_hat",))["y_hat"]
                 if not reconstruct:
                     return y_hat, True, None
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, gpu_side, "decompress")
 
@@ -1442,11 +1474,14 @@ class VAEformer(nn.Module):
         step = self._step_arg(step, box)
         self.entropy_bottleneck._check()
         self.gaussian_conditional._check()
-        out = torch.stack([self._decompress_frame(strings[0][b], strings[1][b], shape, rec, channels=channels, box=box,
-                                                  step=step)
-                           for b in range(len(strings[0]))])
+        B = len(strings[0])
         if not rec:
-            return out
+            return torch.stack([self._decompress_frame(strings[0][b], strings[1][b], shape, False) for b in range(B)])
+        # the batch result is allocated once and every frame's un-embed stores into its slice (no stack copy)
+        out = torch.empty((B,) + self._decoded_shape(channels, box, step), device=self.device, dtype=torch.float32)
+        for b in range(B):
+            self._decompress_frame(strings[0][b], strings[1][b], shape, True, channels=channels, box=box, step=step,
+                                   out=out[b])
         return {"x_hat": out}
 
     @torch.no_grad()
