@@ -73,6 +73,9 @@ SIGNATURES = {
     "cra5_recon_error_slab_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cra5_recon_error_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p,
                                      c_void_p]),
+    "cra5_time_accumulate_f32": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cra5_time_finish_f32": (c_int, [c_size_t, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
     "cra5_transpose_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "cra5_pixel_shuffle_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "cra5_conv_im2col_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 12 + [c_void_p]),

@@ -633,6 +633,115 @@ class cra5_api:
         return self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights),
                                            list(zip(time_stamps, frames, paths)))
 
+    def _aggregate_one(self, path, denorm, channels, box, step, frame_shape, acc, seq):
+        """One frame of aggregate_batch on the calling frame thread: .bin -> x_hat (or its subset) -> folded into the
+        group's device accumulators as turn `seq`, on this frame's stream.  Nothing crosses to the host."""
+        lstrings, shape = self._read_bin(path)
+        with torch.no_grad():
+            t_d = time.perf_counter()
+            x_hat = self.net._decompress_frame(lstrings[0][0], lstrings[1][0], shape, True,
+                                               mean=self._mean_flat if denorm else None,
+                                               std=self._std_flat if denorm else None, channels=channels, box=box,
+                                               step=step)
+            self._log("decompress", t_d)
+            t_a = time.perf_counter()
+            if tuple(x_hat.shape[-3:]) != frame_shape or x_hat.numel() != frame_shape[0] * frame_shape[1] * frame_shape[2]:
+                raise ValueError(f"{path}: the reconstruction is {tuple(x_hat.shape)}, the accumulators {frame_shape}")
+            acc.add(x_hat.reshape(frame_shape), seq=seq)
+            self._log("accumulate", t_a)
+
+    def aggregate_batch(self, time_stamps=None, paths=None, stats=("mean", "std", "min", "max"), groups=None, ddof=0,
+                        variables=None, region=None, stride=None, return_format='de_normalized', workers=12, to_host=True):
+        """Per-grid-point statistics over time of many decoded frames (a daily or monthly mean, the spread, the extremes),
+        reduced on the GPU: every .bin is decoded through the frame pipeline exactly as decode_batch decodes it, and
+        instead of crossing the host link the reconstruction is folded into device accumulators (cra5_amd.timestats,
+        csrc/timestats.hip) on the frame's own stream, in frame order.  Only the finished statistics come back, once.
+          stats: any of "mean", "std", "min", "max" (timestats: float64 sums, mean = f32(s / n), std = f32(sqrt(max(0,
+            (q - s * s / n) / (n - ddof)))), min / max propagate NaN).  mean, min and max equal a sequential float64 numpy
+            loop over decode_batch's frames bit for bit, std to one fp32 ulp; every result is bit-identical from run to
+            run and for every `workers`.
+          groups: None, or one hashable label per frame (ts[:10] of hourly files: daily statistics) - one result per
+            distinct label, the labels in order of first appearance; within a group the frames apply in index order.
+          variables / region / stride / return_format ('de_normalized' | 'normalized'): as in decode_batch.
+        Returns a dict: variables, lat, lon (also for the full grid), n (int; with groups an int64 [G] array), groups
+        (the labels, when given) and per statistic a HOST float32 array [C', Hb, Wb] ([G, C', Hb, Wb] with groups), or
+        with to_host=False a device tensor of that shape.  A frame that fails (a missing file, a StreamDesyncError) ends
+        the call with that frame's error."""
+        from .timestats import TimeStats, check_stats
+        if paths is None:
+            if time_stamps is None:
+                raise ValueError("aggregate_batch needs time_stamps or paths")
+            paths = [f'{self.local_root}/CRA5/{ts[:4]}/{ts}.bin' for ts in time_stamps]
+        paths = list(paths)
+        if not paths:
+            raise ValueError("aggregate_batch: no frame given")
+        stats = check_stats(stats, ddof)
+        if return_format == 'latent':
+            raise ValueError("aggregate_batch: return_format='latent' is the latent, not a reconstruction to reduce; "
+                             "use 'de_normalized' or 'normalized'")
+        if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
+            raise ValueError(f"unknown return_format {return_format!r}")
+        denorm = return_format != 'normalized'
+        if groups is None:
+            labels, member = [None], [0] * len(paths)
+        else:
+            groups = list(groups)
+            if len(groups) != len(paths):
+                raise ValueError(f"aggregate_batch: groups holds {len(groups)} labels for {len(paths)} frames")
+            labels = list(dict.fromkeys(groups))
+            index = {lab: g for g, lab in enumerate(labels)}
+            member = [index[lab] for lab in groups]
+        counts = [member.count(g) for g in range(len(labels))]
+        if "std" in stats and min(counts) - ddof < 1:
+            g = counts.index(min(counts))
+            raise ValueError(f"aggregate_batch: std with ddof = {ddof} needs more than {ddof} frame(s) per group; "
+                             + (f"group {labels[g]!r} holds {counts[g]}" if groups is not None else f"{counts[g]} given"))
+        channels, box, step, meta = self._subset(variables, region, stride)
+        if meta is None:
+            H, W = self.net.cfg['img_size']
+            g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W)
+            meta = dict(variables=[self.channels_to_vname.get(c, str(c)) for c in range(self.net.cfg['out_chans'])],
+                        lat=g["lat"], lon=g["lon"])
+        frame_shape = (len(meta["variables"]), len(meta["lat"]), len(meta["lon"]))
+        self.net._require_gpu()
+
+        # every accumulator before the first decode: running out of device memory shows here
+        accs = [TimeStats(frame_shape, stats=stats, device=self.net.device, ddof=ddof) for _ in labels]
+        seqs, seen = [], [0] * len(labels)
+        for g in member:
+            seqs.append(seen[g])
+            seen[g] += 1
+
+        def one(i):
+            try:
+                self._aggregate_one(paths[i], denorm, channels, box, step, frame_shape, accs[member[i]], seqs[i])
+            except BaseException as e:
+                for a in accs:       # nobody waits for this frame's turn, and the call ends with this frame's error
+                    a.abort(e)
+                raise
+        self._pipeline(workers).map(one, list(range(len(paths))))
+
+        res = dict(meta)
+        done = [a.result() for a in accs]
+        if groups is not None:
+            res["groups"] = labels
+            res["n"] = np.array([d["n"] for d in done], dtype=np.int64)
+        else:
+            res["n"] = int(done[0]["n"])
+        if not to_host:
+            for s in stats:
+                res[s] = torch.stack([d[s] for d in done]) if groups is not None else done[0][s]
+            return res
+        t0 = time.perf_counter()
+        pin = self.net._pinned("api_x_out", frame_shape, torch.float32)
+        for s in stats:
+            host = np.empty(((len(labels),) if groups is not None else ()) + frame_shape, dtype=np.float32)
+            for g, d in enumerate(done):
+                ops.copy_d2h_staged(host[g] if groups is not None else host, d[s], pin, threads=self.runtime.copy_threads)
+            res[s] = host
+        self._log("d2h", t0)
+        return res
+
     # ------------------------------------------------------------------ decode
     def _read_bin(self, bin_path):
         with Path(bin_path).open("rb") as f:

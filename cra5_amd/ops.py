@@ -711,6 +711,63 @@ def recon_error(x_hat, x, lat_w=None, out=None):
     return out
 
 
+TIME_ACCUMULATORS = (("sum", torch.float64), ("sumsq", torch.float64), ("min", torch.float32), ("max", torch.float32))
+
+
+def _time_acc(what, acc, shape, device):
+    """The accumulator dict of time_accumulate / time_finish, checked: contiguous device tensors of `shape`."""
+    if not isinstance(acc, dict) or not acc or not set(acc) <= {k for k, _ in TIME_ACCUMULATORS}:
+        raise ValueError(f"{what}: acc must be a dict with any of 'sum', 'sumsq' (fp64), 'min', 'max' (fp32), at least one "
+                         f"(got {sorted(acc) if isinstance(acc, dict) else type(acc).__name__})")
+    for k, dt in TIME_ACCUMULATORS:
+        t = acc.get(k)
+        if t is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise TypeError(f"{what}: acc[{k!r}] must be a contiguous {dt} device tensor")
+        if tuple(t.shape) != tuple(shape) or t.device != device:
+            raise ValueError(f"{what}: acc[{k!r}] is {tuple(t.shape)} on {t.device}, the frame {tuple(shape)} on {device}")
+    return [acc.get(k) for k, _ in TIME_ACCUMULATORS]
+
+
+def time_accumulate(x, acc, first):
+    """cra5_time_accumulate_f32: fold the contiguous fp32 device tensor `x` into the accumulators `acc` - a dict with any
+    of "sum" / "sumsq" (fp64) and "min" / "max" (fp32), each a contiguous device tensor of x's shape.  first: store
+    (sum = x, sumsq = x * x, min = max = x; the accumulators may be uninitialised), else update.  On the current stream;
+    consecutive calls on the same accumulators must run one after another on the device."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+        raise TypeError("time_accumulate takes a contiguous fp32 device tensor")
+    if x.numel() == 0:
+        raise ValueError("time_accumulate: the frame is empty")
+    s, q, lo, hi = _time_acc("time_accumulate", acc, x.shape, x.device)
+    check(lib().cra5_time_accumulate_f32(_p(x), x.numel(), 1 if first else 0, _p(s), _p(q), _p(lo), _p(hi), _stream()),
+          "cra5_time_accumulate_f32")
+    return acc
+
+
+def time_finish(acc, count, ddof=0, want=("mean", "std")):
+    """cra5_time_finish_f32 on the accumulators of `count` time_accumulate calls -> {"mean": fp32 device tensor,
+    "std": ...} for the names in `want`: mean = sum / count, std = sqrt(max(0, (sumsq - sum * sum / count) /
+    (count - ddof))), in fp64, rounded to fp32 at the end.  mean needs acc["sum"], std acc["sum"] and acc["sumsq"];
+    count - ddof >= 1.  On the current stream."""
+    want = tuple(want)
+    if not want or not set(want) <= {"mean", "std"}:
+        raise ValueError(f"time_finish: want must name 'mean' and / or 'std' (got {want!r})")
+    if not isinstance(acc, dict) or acc.get("sum") is None or ("std" in want and acc.get("sumsq") is None):
+        raise ValueError("time_finish: mean needs acc['sum'], std needs acc['sum'] and acc['sumsq']")
+    count, ddof = int(count), int(ddof)
+    if ddof < 0 or count - ddof < 1:
+        raise ValueError(f"time_finish: count - ddof must be >= 1 with ddof >= 0 (count {count}, ddof {ddof})")
+    ref = acc["sum"]
+    if not (isinstance(ref, torch.Tensor) and ref.is_cuda):
+        raise TypeError("time_finish takes device accumulators")
+    s, q, _, _ = _time_acc("time_finish", acc, ref.shape, ref.device)
+    out = {k: torch.empty(ref.shape, device=ref.device, dtype=torch.float32) for k in want}
+    check(lib().cra5_time_finish_f32(ref.numel(), count, ddof, _p(s), _p(q) if "std" in want else None, _p(out.get("mean")),
+                                     _p(out.get("std")), _stream()), "cra5_time_finish_f32")
+    return out
+
+
 def transpose(x, out=None):
     _dev(x, out)
     R, Cc = x.shape

@@ -328,6 +328,25 @@ size_t cra5_recon_error_slab_bytes(int C, int H, int W);
 int cra5_recon_error_f32(const float *x_hat, const float *x, int C, int H, int W, const float *lat_w, double *slab,
                          size_t slab_bytes, double *out, void *stream);
 
+/* Per-grid-point statistics over many frames (csrc/timestats.hip): flat fp32 frames x of n elements, accumulators of the
+ * same n elements - sum / sumsq fp64, mn / mx fp32.  Each accumulator pointer may be NULL (that statistic is not kept: it
+ * is neither read nor written); at least one is given.  Per element i, v = (double)x[i]:
+ *   first != 0:  sum = v,  sumsq = v * v,  mn = mx = x[i]   (plain stores: no memset, uninitialised accumulators are fine)
+ *   first == 0:  sum += v, sumsq += v * v, mn = min(mn, x[i]), mx = max(mx, x[i])
+ * v * v is exact in fp64, every update rounds once: calls in frame order on one stream (or chained by events) leave in
+ * sum / sumsq the bits of a sequential float64 loop.  min / max return NaN if either operand is NaN (numpy's minimum /
+ * maximum); the sign of a zero result is unspecified.  Non-finite samples are not filtered.  16-byte aligned bases take
+ * the float4 / double2 path, anything else goes element by element; pointers aligned to their element size.
+ * cra5_time_finish_f32 (mean / std may each be NULL, not both), every operation in fp64, uncontracted, in this order:
+ *   mean[i] = (float)(sum[i] / count)
+ *   std[i]  = (float)sqrt(max(0, (sumsq[i] - sum[i] * sum[i] / count) / (count - ddof)))
+ * std needs sum and sumsq, mean needs sum; ddof >= 0 and count - ddof >= 1.  CRA5_ERR_ARG, before any device work, for
+ * n == 0, no accumulator / no output, std without sumsq, count - ddof < 1 and misaligned pointers. */
+int cra5_time_accumulate_f32(const float *x, size_t n, int first, double *sum, double *sumsq, float *mn, float *mx,
+                             void *stream);
+int cra5_time_finish_f32(size_t n, long long count, int ddof, const double *sum, const double *sumsq, float *mean,
+                         float *stdv, void *stream);
+
 /* out[c][r] = in[r][c] (token-major <-> NCHW plumbing, vit_nlc.py:484, 684). */
 int cra5_transpose_f32(const float *in, int ld_in, float *out, int ld_out, int rows, int cols,
                        void *stream);
