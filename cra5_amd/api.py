@@ -205,21 +205,29 @@ class cra5_api:
     # with c % s_lon == 0, r / c counted on the GLOBAL grid - stride=6 is the 121 x 240 grid at 1.5 deg, poles included.
     # No interpolation, no averaging: with `full` the full decode of the same file under the same settings,
     # x_hat == full[channels][:, kept_rows][:, :, kept_cols] as bit patterns.  None / 1 / (1, 1): no thinning.
+    # coarsen=k or (k_lat, k_lon) (not together with a stride): at the very points stride=k keeps, the AREA-WEIGHTED MEAN
+    # of the full decode over the coarse cell round each point - first-order conservative remapping, computed on the GPU
+    # in fixed float64 arithmetic ("Coarsening"; (721 - 1) % k_lat == 0 and 1440 % k_lon == 0):
+    # coarsen=6 is the conservative 1.5 deg field, 1 / 36 of the bytes.  The dict also carries coarsen, lat_bnds, lon_bnds.
     grid_box = staticmethod(subset.grid_box)
     resolve_variables = staticmethod(subset.resolve_variables)
 
-    def _subset(self, variables, region, stride=None):
-        """-> (channel indices | None, grid box | None, stride (s_lat, s_lon) | None, the result dict's extra keys) for
-        the model; (None, None, None, None) without a subset."""
+    def _subset(self, variables, region, stride=None, coarsen=None):
+        """-> (channel indices | None, grid box | None, dict(step=(s_lat, s_lon) | None, coarsen=(k_lat, k_lon) | None) -
+        the model's keyword arguments -, the result dict's extra keys); (None, None, both None, None) without a subset."""
         H, W = self.net.cfg['img_size']
-        step = subset.resolve_stride(stride, W)
-        if variables is None and region is None and step is None:
-            return None, None, None, None
+        step, k = subset._stride_or_coarsen(stride, coarsen, H, W)
+        if variables is None and region is None and step is None and k is None:
+            return None, None, dict(step=None, coarsen=None), None
         chans = subset.resolve_variables(variables, self.vname_to_channels)
-        g = subset.grid_box(region if region is not None else (-90.0, 90.0, 0.0, 360.0), H, W, stride=step)
+        g = subset.grid_box(region if region is not None else (-90.0, 90.0, 0.0, 360.0), H, W, stride=step, coarsen=k)
         names = [self.channels_to_vname.get(c, str(c)) for c in (chans if chans is not None else range(self.net.cfg['out_chans']))]
         channels, box = self.net._subset_args(chans, g["box"] if region is not None else None)
-        return channels, box, self.net._step_arg(step, box), dict(variables=names, lat=g["lat"], lon=g["lon"])
+        meta = dict(variables=names, lat=g["lat"], lon=g["lon"])
+        if k is not None:
+            meta.update(coarsen=k, lat_bnds=g["lat_bnds"], lon_bnds=g["lon_bnds"])
+        step = self.net._step_arg(step, box)
+        return channels, box, dict(step=step, coarsen=self.net._coarsen_arg(k, box, step)), meta
 
     def get_mean_std(self):
         """cra5_api.py:243-261."""
@@ -482,9 +490,9 @@ class cra5_api:
         return self._pipeline(workers).map(lambda it: self._encode_one(it[0], it[1], save_root, write),
                                            list(zip(time_stamps, frames)))
 
-    def _decode_one(self, i, path, denorm, out=None, sink=None, channels=None, box=None, step=None):
+    def _decode_one(self, i, path, denorm, out=None, sink=None, channels=None, box=None, step=None, coarsen=None):
         """One frame of the batch decode on the calling frame thread: .bin -> x_hat (or its subset: canonical channels /
-        box / step of VAEformer._subset_args / _step_arg) -> this thread's pinned buffer -> `sink` / `out[i]` / a fresh
+        box / step / coarsen of VAEformer._subset_args / _step_arg / _coarsen_arg) -> this thread's pinned buffer -> `sink` / `out[i]` / a fresh
         array."""
         lstrings, shape = self._read_bin(path)
         with torch.no_grad():
@@ -492,7 +500,7 @@ class cra5_api:
             x_hat = self.net._decompress_frame(lstrings[0][0], lstrings[1][0], shape, True,
                                                mean=self._mean_flat if denorm else None,
                                                std=self._std_flat if denorm else None, channels=channels, box=box,
-                                               step=step)
+                                               step=step, coarsen=coarsen)
             self._log("decompress", t_d)
             C, H, W = x_hat.shape[-3:]
             pin = self.net._pinned("api_x_out", (C, H, W), torch.float32)
@@ -550,7 +558,7 @@ class cra5_api:
         return self._pipeline(workers).map(one, [(i, ts, a) for i, (ts, a) in enumerate(zip(time_stamps, frames))])
 
     def decode_batch(self, time_stamps=None, paths=None, return_format='de_normalized', out=None, workers=12, sink=None,
-                     variables=None, region=None, stride=None):
+                     variables=None, region=None, stride=None, coarsen=None):
         """decode_from_bin for many frames.  Returns a list of HOST float32 arrays [C, H, W] (views of `out`
         [n, C, H, W] when given, fresh arrays otherwise); the D2H of each reconstruction goes through the
         decoding thread's pinned buffer and overlaps the other frames' work.  `sink(i, frame)`: called on the decoding
@@ -559,26 +567,31 @@ class cra5_api:
         a long decode loop needs no [n, C, H, W] host array.
         variables / region / stride (decode_from_bin): every frame is the subset [C', Hb, Wb] - `out` must then be
         [n, C', Hb, Wb], `sink` gets [C', Hb, Wb] views; grid_box(region, stride=stride) gives its lat / lon (with a
-        stride Hb / Wb count the kept rows / columns: stride=6 over the globe is [C', 121, 240])."""
+        stride Hb / Wb count the kept rows / columns: stride=6 over the globe is [C', 121, 240]).
+        coarsen (decode_from_bin): the same shapes as stride=coarsen, every point the area-weighted mean of its coarse
+        cell - 1 / (k_lat * k_lon) of the bytes cross the host link; grid_box(region, coarsen=coarsen) gives lat / lon
+        and the cells' lat_bnds / lon_bnds."""
         if paths is None:
             paths = [f'{self.local_root}/CRA5/{ts[:4]}/{ts}.bin' for ts in time_stamps]
         if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
             raise ValueError(f"unknown return_format {return_format!r}")
         denorm = return_format != 'normalized'
         self.net._require_gpu()
-        channels, box, step, meta = self._subset(variables, region, stride)
+        channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
         shape = None
         if meta is not None:
             shape = (len(meta["variables"]), len(meta["lat"]), len(meta["lon"]))
         self._check_out(out, len(paths), shape)
 
-        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box, step),
+        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box, **sel),
                                            list(enumerate(paths)))
 
-    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights):
+    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, coarsen=None):
         """One frame of evaluate_batch on the calling frame thread: the truth is staged once into this thread's device
         frame buffer; the reconstruction comes from the in-memory strings (bin_path None) or from `bin_path`, and only
-        the per-channel statistics leave the device."""
+        the per-channel statistics leave the device.  coarsen = (k_lat, k_lon): both frames are coarsened on the device
+        by the same kernel (the reconstruction inside its decode, the truth by VAEformer.coarsen_frame) and compared on
+        the coarse grid."""
         from . import metrics
         if bin_path is None:
             enc, x = self._encode_staged(ts, arr, save_root, write=save_root is not None)
@@ -596,13 +609,22 @@ class cra5_api:
         with torch.no_grad():
             t_d = time.perf_counter()
             x_hat = self.net._decompress_frame(strings[0][0], strings[1][0], shape, True,
-                                               mean=self._mean_flat, std=self._std_flat)
+                                               mean=self._mean_flat, std=self._std_flat, coarsen=coarsen)
             self._log("decompress", t_d)
             t_m = time.perf_counter()
             C, H, W = x.shape[-3:]
-            if tuple(x_hat.shape[-3:]) != (C, H, W):
-                raise ValueError(f"{ts}: the reconstruction is {tuple(x_hat.shape[-3:])}, the truth frame {(C, H, W)}")
-            err = metrics.reconstruction_error(x_hat.reshape(C, H, W), x.reshape(C, H, W), lat_weights=lat_weights)
+            x = x.reshape(C, H, W)
+            if coarsen is not None:
+                if (C, H, W) != (self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size']):
+                    raise ValueError(f"{ts}: the truth frame is {(C, H, W)}, the model's grid "
+                                     f"{(self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size'])}")
+                Ho, Wo = self.net._decoded_shape(None, None, coarsen=coarsen)[-2:]
+                # this thread's persistent workspace, like the decode's own buffers: no allocation per frame
+                x = self.net.coarsen_frame(x.contiguous(), coarsen, out=self.net._buf("eval_truth_coarse", (C, Ho, Wo)))
+            Ce, He, We = x.shape
+            if tuple(x_hat.shape[-3:]) != (Ce, He, We):
+                raise ValueError(f"{ts}: the reconstruction is {tuple(x_hat.shape[-3:])}, the truth frame {(Ce, He, We)}")
+            err = metrics.reconstruction_error(x_hat.reshape(Ce, He, We), x, lat_weights=lat_weights)
             self._log("metrics", t_m)
         std = self._std_flat.detach().cpu().numpy().astype(np.float64)
         rep = dict(time_stamp=ts, variables=[self.channels_to_vname.get(c, str(c)) for c in range(C)])
@@ -612,7 +634,8 @@ class cra5_api:
         rep["compression_ratio"] = C * H * W * 4 / n_bytes
         return rep
 
-    def evaluate_batch(self, time_stamps, data=None, bins=None, save_root=None, workers=12, lat_weights="era5"):
+    def evaluate_batch(self, time_stamps, data=None, bins=None, save_root=None, workers=12, lat_weights="era5",
+                       coarsen=None):
         """Per-variable reconstruction error of many frames, through the frame pipeline, without copying any
         reconstruction to the host.  Truth frames: `data` (a matching list of host arrays / tensors, physical units) or
         the NetCDF files of `time_stamps`.
@@ -623,17 +646,30 @@ class cra5_api:
         Returns one dict per frame: time_stamp, variables (channel names), the statistics of
         metrics.reconstruction_error (float64 [C] arrays in physical units; nonfinite int64 [C]), rmse_norm = rmse / std
         (the codec's per-channel normalisation std), bin_bytes (the container size, header included) and
-        compression_ratio = C * H * W * 4 / bin_bytes."""
+        compression_ratio = C * H * W * 4 / bin_bytes.
+        coarsen=k or (k_lat, k_lon): the error at the coarse resolution (coarsen=6: 1.5 deg) - truth and reconstruction are
+        both area-averaged on the device (decode_from_bin's coarsen) and compared on the [C, Ho, Wo] grid, "era5" weights
+        being latitude_weights(Ho); the reports also carry coarsen, lat and lon of that grid.  compression_ratio stays
+        that of the full frame."""
         self.net._require_gpu()
+        H, W = self.net.cfg['img_size']
+        k = self.net._coarsen_arg(coarsen, None)
+        extra = {}
+        if k is not None:
+            g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W, coarsen=k)
+            extra = dict(coarsen=k, lat=g["lat"], lon=g["lon"])
         n = len(time_stamps)
         frames = list(data) if data is not None else [None] * n
         if len(frames) != n or (bins is not None and len(bins) != n):
             raise ValueError("evaluate_batch: time_stamps, data and bins must have the same length")
         paths = list(bins) if bins is not None else [None] * n
-        return self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights),
+        reps = self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights, k),
                                            list(zip(time_stamps, frames, paths)))
+        for r in reps:
+            r.update(extra)
+        return reps
 
-    def _aggregate_one(self, path, denorm, channels, box, step, frame_shape, acc, seq):
+    def _aggregate_one(self, path, denorm, channels, box, sel, frame_shape, acc, seq):
         """One frame of aggregate_batch on the calling frame thread: .bin -> x_hat (or its subset) -> folded into the
         group's device accumulators as turn `seq`, on this frame's stream.  Nothing crosses to the host."""
         lstrings, shape = self._read_bin(path)
@@ -642,7 +678,7 @@ class cra5_api:
             x_hat = self.net._decompress_frame(lstrings[0][0], lstrings[1][0], shape, True,
                                                mean=self._mean_flat if denorm else None,
                                                std=self._std_flat if denorm else None, channels=channels, box=box,
-                                               step=step)
+                                               **sel)
             self._log("decompress", t_d)
             t_a = time.perf_counter()
             if tuple(x_hat.shape[-3:]) != frame_shape or x_hat.numel() != frame_shape[0] * frame_shape[1] * frame_shape[2]:
@@ -651,7 +687,8 @@ class cra5_api:
             self._log("accumulate", t_a)
 
     def aggregate_batch(self, time_stamps=None, paths=None, stats=("mean", "std", "min", "max"), groups=None, ddof=0,
-                        variables=None, region=None, stride=None, return_format='de_normalized', workers=12, to_host=True):
+                        variables=None, region=None, stride=None, return_format='de_normalized', workers=12, to_host=True,
+                        coarsen=None):
         """Per-grid-point statistics over time of many decoded frames (a daily or monthly mean, the spread, the extremes),
         reduced on the GPU: every .bin is decoded through the frame pipeline exactly as decode_batch decodes it, and
         instead of crossing the host link the reconstruction is folded into device accumulators (cra5_amd.timestats,
@@ -662,8 +699,10 @@ class cra5_api:
             run and for every `workers`.
           groups: None, or one hashable label per frame (ts[:10] of hourly files: daily statistics) - one result per
             distinct label, the labels in order of first appearance; within a group the frames apply in index order.
-          variables / region / stride / return_format ('de_normalized' | 'normalized'): as in decode_batch.
-        Returns a dict: variables, lat, lon (also for the full grid), n (int; with groups an int64 [G] array), groups
+          variables / region / stride / coarsen / return_format ('de_normalized' | 'normalized'): as in decode_batch -
+            with coarsen=k the statistics are those of the area-averaged frames, in 1 / (k_lat * k_lon) of the accumulator
+            memory and of the final host copy.
+        Returns a dict: variables, lat, lon (also for the full grid; with coarsen also coarsen, lat_bnds, lon_bnds), n (int; with groups an int64 [G] array), groups
         (the labels, when given) and per statistic a HOST float32 array [C', Hb, Wb] ([G, C', Hb, Wb] with groups), or
         with to_host=False a device tensor of that shape.  A frame that fails (a missing file, a StreamDesyncError) ends
         the call with that frame's error."""
@@ -696,7 +735,7 @@ class cra5_api:
             g = counts.index(min(counts))
             raise ValueError(f"aggregate_batch: std with ddof = {ddof} needs more than {ddof} frame(s) per group; "
                              + (f"group {labels[g]!r} holds {counts[g]}" if groups is not None else f"{counts[g]} given"))
-        channels, box, step, meta = self._subset(variables, region, stride)
+        channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
         if meta is None:
             H, W = self.net.cfg['img_size']
             g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W)
@@ -714,7 +753,7 @@ class cra5_api:
 
         def one(i):
             try:
-                self._aggregate_one(paths[i], denorm, channels, box, step, frame_shape, accs[member[i]], seqs[i])
+                self._aggregate_one(paths[i], denorm, channels, box, sel, frame_shape, accs[member[i]], seqs[i])
             except BaseException as e:
                 for a in accs:       # nobody waits for this frame's turn, and the call ends with this frame's error
                     a.abort(e)
@@ -758,14 +797,14 @@ class cra5_api:
         with torch.no_grad():
             return self.net.decompress(lstrings, shape, return_format='latent')
 
-    def latent_to_reconstruction(self, y_hat, variables=None, region=None, stride=None):
-        """cra5_api.py:146-151 (normalised units).  variables / region / stride: that subset (decode_from_bin)."""
-        channels, box, step, _ = self._subset(variables, region, stride)
+    def latent_to_reconstruction(self, y_hat, variables=None, region=None, stride=None, coarsen=None):
+        """cra5_api.py:146-151 (normalised units).  variables / region / stride / coarsen: that subset (decode_from_bin)."""
+        channels, box, sel, _ = self._subset(variables, region, stride, coarsen)
         with torch.no_grad():
-            return self.net.decode_latent(y_hat, channels=channels, box=box, step=step)
+            return self.net.decode_latent(y_hat, channels=channels, box=box, **sel)
 
     def decode_from_bin(self, time_stamp=None, custom_path=None, return_format='de_normalized', to_host=False, out=None,
-                        variables=None, region=None, stride=None):
+                        variables=None, region=None, stride=None, coarsen=None):
         """cra5_api.py:153-192.  `to_host=True` (or `out=` a float32 array of the frame's shape): `x_hat` comes back
         as a HOST numpy array through the pinned staging buffer instead of a device tensor.
         variables: names of channel_vname_mapping() (e.g. ["z_500", "t_850", "t2m"]), output channels in that order;
@@ -776,13 +815,21 @@ class cra5_api:
         the columns c with c % s_lon == 0, r / c counted on the GLOBAL grid (a region's thinned decode is a sub-block of the
         globe's; 1440 % s_lon must be 0): decode_from_bin(ts, stride=6) is the 121 x 240 grid at 1.5 deg.  Again the slice
         of the full decode, bit for bit: x_hat == full[channels][:, kept_rows][:, :, kept_cols]; `lat` / `lon` are those of
-        the kept rows / columns, `out` is checked against the thinned shape.  None / 1 / (1, 1): no thinning."""
-        if return_format == 'latent' and (variables is not None or region is not None or stride is not None):
-            raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region / stride "
-                             "select a subset of the reconstruction")
+        the kept rows / columns, `out` is checked against the thinned shape.  None / 1 / (1, 1): no thinning.
+        coarsen: a positive int or (k_lat, k_lon), not together with a stride; 720 % k_lat == 0 and 1440 % k_lon == 0 - at
+        the points stride=coarsen keeps, the area-weighted mean of the full decode over the coarse cell round each point
+        (latitude band lat -+ k_lat * 0.125 deg clipped at the poles, longitude band lon -+ k_lon * 0.125 deg; first-order
+        conservative remapping): decode_from_bin(ts, coarsen=6) is the conservative 1.5 deg field
+        [C', 121, 240].  Computed on the GPU in fixed float64 arithmetic: bit-identical from run to run, a region's result
+        the sub-block of the globe's; NaN / inf in a window propagate.  The dict also carries `coarsen`, `lat_bnds`
+        [Hb, 2] (north, south) and `lon_bnds` [Wb, 2] (west, east)."""
+        if return_format == 'latent' and (variables is not None or region is not None or stride is not None
+                                          or coarsen is not None):
+            raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region / stride / "
+                             "coarsen select a subset of the reconstruction")
         if return_format not in ('latent', 'normalized', 'de_normalized', 'de_normlized'):
             raise ValueError(f"unknown return_format {return_format!r}")
-        channels, box, step, meta = self._subset(variables, region, stride)
+        channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
         bin_path = custom_path or f'{self.local_root}/CRA5/{time_stamp[:4]}/{time_stamp}.bin'
         decoding_start = time.time()
         lstrings, shape = self._read_bin(bin_path)
@@ -791,11 +838,11 @@ class cra5_api:
             if return_format == 'latent':
                 return y_hat
             if return_format == 'normalized':
-                x_hat = self.net.decode_latent(y_hat, channels=channels, box=box, step=step)
+                x_hat = self.net.decode_latent(y_hat, channels=channels, box=box, **sel)
             else:
                 # fused de-normalisation in the overlap-add store
                 x_hat = self.net._decode_guarded(y_hat[0], mean=self._mean_flat, std=self._std_flat, channels=channels,
-                                                 box=box, step=step)
+                                                 box=box, **sel)
             if to_host or out is not None:
                 src = x_hat.reshape(x_hat.shape[-3:]).contiguous()
                 if out is None:

@@ -669,6 +669,66 @@ def crop(src, r0, Hb, c0, Wb, out=None):
     return out
 
 
+def coarsen_tables(plan, device):
+    """The tables of ops.coarsen for a subset.coarsen_plan: its geometry plus device copies of row0 / ntap (int32 [Ho])
+    and rw (fp64 [Ho, k_lat + 1])."""
+    t = dict(plan)
+    t["row0"] = torch.as_tensor(np.ascontiguousarray(plan["row0"], dtype=np.int32)).to(device)
+    t["ntap"] = torch.as_tensor(np.ascontiguousarray(plan["ntap"], dtype=np.int32)).to(device)
+    t["rw"] = torch.as_tensor(np.ascontiguousarray(plan["rw"], dtype=np.float64)).to(device)
+    return t
+
+
+def coarsen(x, plan_tables, out=None, chan_map=None):
+    """cra5_coarsen_f32: the area-weighted mean of x - contiguous fp32 [C, Hs, Ws], the source box plan["src_box"] of an
+    H x W global grid - onto the plan's output points -> contiguous fp32 [C_out, Ho, Wo] (`out`, or a fresh tensor).
+    plan_tables: coarsen_tables(subset.coarsen_plan(box, k, H, W), device) - the grid (H, W) is the plan's.  chan_map: int32 device [C_out] - output
+    channel c is source channel chan_map[c] (a variable subset of a full source needs no gather first); None: C_out = C,
+    in order.  The arithmetic is fixed (include/cra5_amd.h): bit-identical from run to run, and a region's result is
+    the sub-block of the globe's."""
+    t = plan_tables
+    _dev(x, out)
+    ok = (isinstance(t, dict) and all(isinstance(t.get(k), torch.Tensor) and t[k].is_cuda and t[k].is_contiguous()
+                                      for k in ("row0", "ntap", "rw"))
+          and t["row0"].dtype == torch.int32 and t["ntap"].dtype == torch.int32 and t["rw"].dtype == torch.float64)
+    if not ok:
+        raise ValueError("coarsen: plan_tables must come from ops.coarsen_tables (row0 / ntap int32, rw fp64 contiguous "
+                         "device tensors)")
+    Ho, Wo = int(t["Ho"]), int(t["Wo"])
+    ky, kx = (int(v) for v in t["k"])
+    sr0, sr1, sc0, snc = (int(v) for v in t["src_box"])
+    H, W = (int(v) for v in t["grid"])
+    if any(t[k].device != x.device for k in ("row0", "ntap", "rw")):
+        raise ValueError(f"coarsen: the tables are on {t['row0'].device}, x on {x.device}")
+    if tuple(t["row0"].shape) != (Ho,) or tuple(t["ntap"].shape) != (Ho,) or t["rw"].dim() != 2 or t["rw"].shape[0] != Ho:
+        raise ValueError(f"coarsen: the tables do not belong to a plan of {Ho} output rows")
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous() or tuple(x.shape[1:]) != (sr1 - sr0, snc):
+        raise ValueError(f"coarsen: x must be a contiguous fp32 [C, {sr1 - sr0}, {snc}] tensor - the plan's source box "
+                         f"{(sr0, sr1, sc0, snc)} (got {tuple(x.shape)} {x.dtype})")
+    C = x.shape[0]
+    if chan_map is not None:
+        if not (isinstance(chan_map, torch.Tensor) and chan_map.is_cuda and chan_map.dtype == torch.int32
+                and chan_map.dim() == 1 and chan_map.is_contiguous() and chan_map.numel() > 0
+                and chan_map.device == x.device):
+            raise ValueError("coarsen: chan_map must be a contiguous int32 vector on x's device")
+        C_out = chan_map.numel()
+    else:
+        C_out = C
+    if out is None:
+        out = torch.empty((C_out, Ho, Wo), device=x.device, dtype=torch.float32)
+    if not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (C_out, Ho, Wo)
+            and out.device == x.device):
+        raise ValueError(f"coarsen: out must be a contiguous fp32 [{C_out}, {Ho}, {Wo}] tensor on x's device")
+    ev = TIMER.start() if TIMER is not None else None
+    check(lib().cra5_coarsen_f32(_p(x), C, sr1 - sr0, snc, sr0, sc0, H, W, 1 if (sc0 == 0 and snc == W) else 0,
+                                 int(t["rows"][0]), ky, Ho, int(t["cols"][0]), kx, Wo, _p(t["row0"]), _p(t["ntap"]),
+                                 _p(t["rw"]), t["rw"].shape[1], _p(chan_map), C_out, _p(out), _stream()),
+          "cra5_coarsen_f32")
+    if ev is not None:
+        TIMER.stop("coarsen", ev, 4.0 * (C_out * (sr1 - sr0) * snc + C_out * Ho * Wo))
+    return out
+
+
 PROBE_PARTIALS = 256     # CRA5_PROBE_PARTIALS
 
 

@@ -4,7 +4,9 @@ Host-side geometry only (no model, no GPU): `grid_box` turns a lat/lon box in de
 `resolve_variables` turns variable names into channel indices, `token_plan` gives the patch-aligned superset of tokens the
 un-embed runs on for a box (VAEformer._decode_frame; DESIGN.md, "Subset decode").  `resolve_stride`, `kept_points`,
 `stride_plan` and `scatter_tables` are the geometry of a thinned grid (every s_lat-th row, every s_lon-th column of the
-global grid): which (token, tap) products of the un-embed a thinned box needs and where each lands.
+global grid): which (token, tap) products of the un-embed a thinned box needs and where each lands.  `resolve_coarsen`
+and `coarsen_plan` are the geometry of the area-weighted (first-order conservative) regrid onto those same points: the
+source box the windows need and the float64 row-weight table of cra5_coarsen_f32 ("Coarsening").
 
 Grid convention (metrics.latitude_weights): row h is latitude 90 - h * 180 / (H - 1) (row 0 = 90 N), column w is longitude
 w * 360 / W (column 0 = Greenwich, eastward).
@@ -56,7 +58,98 @@ def kept_points(box, stride, W=1440):
     return rows, cols
 
 
-def grid_box(region, H=721, W=1440, stride=None):
+def resolve_coarsen(coarsen, H=721, W=1440):
+    """coarsen: None | a positive int | a pair (k_lat, k_lon) of positive ints -> (k_lat, k_lon), or None for "no
+    coarsening" (None, 1, (1, 1)).  resolve_stride's rules: ValueError for anything that is not an integer (a float, a
+    bool, a string), for a value < 1, and for (H - 1) % k_lat != 0 or W % k_lon != 0 - the coarse cells tile the sphere
+    and both poles stay output rows only then."""
+    if coarsen is None:
+        return None
+    parts = coarsen if isinstance(coarsen, (tuple, list, np.ndarray)) else (coarsen, coarsen)
+    try:
+        if len(parts) != 2 or any(isinstance(v, (bool, np.bool_)) for v in parts):
+            raise TypeError
+        ky, kx = (operator.index(v) for v in parts)
+    except TypeError:
+        raise ValueError(f"coarsen must be a positive int or a pair (k_lat, k_lon) of positive ints, got {coarsen!r}") from None
+    if ky < 1 or kx < 1:
+        raise ValueError(f"coarsen {coarsen!r}: factors must be >= 1")
+    if (H - 1) % ky:
+        raise ValueError(f"coarsen {coarsen!r}: ({H} - 1) % k_lat ({ky}) = {(H - 1) % ky} != 0 - the coarse latitude bands "
+                         f"must tile pole to pole with both poles as output rows")
+    if W % kx:
+        raise ValueError(f"coarsen {coarsen!r}: {W} % k_lon ({kx}) = {W % kx} != 0 - the coarse cells must close round the "
+                         f"circle")
+    return None if (ky, kx) == (1, 1) else (ky, kx)
+
+
+def _stride_or_coarsen(stride, coarsen, H, W):
+    """-> (stride (s_lat, s_lon) | None, coarsen (k_lat, k_lon) | None); both given (neither the identity) is refused."""
+    step, k = resolve_stride(stride, W), resolve_coarsen(coarsen, H, W)
+    if step is not None and k is not None:
+        raise ValueError(f"stride {stride!r} and coarsen {coarsen!r}: pass one of the two - coarsen=k returns the grid "
+                         f"points of stride=k, area-averaged instead of sampled")
+    return step, k
+
+
+def _edge_lat(u, H):
+    """Latitude in degrees of the cell edge u half-rows south of the north pole (u = 2 h - 1: the northern edge of row
+    h's cell), clipped to the poles.  ONE expression, monotone in u: min / max of edges commute with it exactly."""
+    return np.clip(90.0 - np.asarray(u, dtype=np.float64) * (90.0 / (H - 1)), -90.0, 90.0)
+
+
+def coarsen_plan(box, k, H=721, W=1440):
+    """The area-weighted mean onto the points a stride k = (k_lat, k_lon) keeps in the box (r0, r1, c0, nc) | None (the
+    globe).  Fine cell of row h: the latitude band between the edges 2 h - 1 and 2 h + 1 (in half-rows from the north
+    pole, clipped to [0, 2 (H - 1)]: the pole rows own half cells); coarse cell of output row R: the band 2 R - k_lat ..
+    2 R + k_lat, clipped; columns c - k_lon / 2 .. c + k_lon / 2 (mod W), the two edge columns of an even k_lon shared
+    half and half with the neighbour cells.  Returns dict(
+      rows, cols: the output points (kept_points: GLOBAL indices), Ho, Wo, k = (k_lat, k_lon), grid = (H, W);
+      src_box (r0, r1, c0, nc): the hull of the windows - rows[0] - k_lat // 2 .. rows[-1] + k_lat // 2 clipped at the
+        poles, columns cols[0] - k_lon // 2 .. cols[-1] + k_lon // 2 eastward, (0, W) - the whole circle from column 0 -
+        when that span reaches W columns;
+      row0, ntap int32 [Ho]: the first GLOBAL source row and the row count of each window;
+      rw float64 [Ho, k_lat + 1], zero-padded: rw[i, t] = V / (S * k_lon) with V = sin(north edge) - sin(south edge) of
+        the overlap of fine row row0[i] + t with the coarse band and S the sum of the window's V, added north to south;
+      lat_bnds float64 [Ho, 2] (north, south edge) and lon_bnds [Wo, 2] (west, east edge: lon -+ k_lon * 180 / W, not
+        wrapped into [0, 360)) in degrees)."""
+    ky, kx = (int(v) for v in k)
+    if ky < 1 or kx < 1 or (H - 1) % ky or W % kx:
+        raise ValueError(f"coarsen {k!r}: need k_lat >= 1 dividing {H} - 1 and k_lon >= 1 dividing {W}")
+    r0, r1, c0, nc = (0, H, 0, W) if box is None else (int(v) for v in box)
+    if not (0 <= r0 < r1 <= H and 0 <= c0 < W and 1 <= nc <= W):
+        raise ValueError(f"box {box!r}: need 0 <= r0 < r1 <= {H}, 0 <= c0 < {W}, 1 <= nc <= {W}")
+    rows, cols = kept_points((r0, r1, c0, nc), (ky, kx), W)
+    Ho, Wo = len(rows), len(cols)
+    umax = 2 * (H - 1)
+    row0 = np.zeros(Ho, dtype=np.int32)
+    ntap = np.zeros(Ho, dtype=np.int32)
+    rw = np.zeros((Ho, ky + 1), dtype=np.float64)
+    lat_bnds = np.zeros((Ho, 2), dtype=np.float64)
+    for i, R in enumerate(int(r) for r in rows):
+        un, us = max(0, 2 * R - ky), min(umax, 2 * R + ky)              # the coarse band's edges, in half-rows
+        hs = [h for h in range(max(0, R - ky // 2 - 1), min(H - 1, R + ky // 2 + 1) + 1)
+              if min(us, 2 * h + 1, umax) > max(un, 2 * h - 1, 0)]       # fine rows with a strip inside it
+        v = [float(np.sin(np.deg2rad(_edge_lat(max(un, 2 * h - 1, 0), H))) -
+                   np.sin(np.deg2rad(_edge_lat(min(us, 2 * h + 1, umax), H)))) for h in hs]
+        if hs != list(range(hs[0], hs[0] + len(hs))) or len(hs) > ky + 1 or min(v) <= 0.0:
+            raise AssertionError(f"coarsen plan: output row {R} has no contiguous window of positive weights")
+        total = 0.0
+        for x in v:                                                       # north to south, one rounding per add
+            total = total + x
+        row0[i], ntap[i] = hs[0], len(hs)
+        rw[i, :len(hs)] = np.array(v, dtype=np.float64) / (total * kx)
+        lat_bnds[i] = (_edge_lat(un, H), _edge_lat(us, H))
+    sr0, sr1 = int(row0[0]), int(row0[-1] + ntap[-1])
+    span = (Wo - 1) * kx + 2 * (kx // 2) + 1
+    sc0, snc = ((int(cols[0]) - kx // 2) % W, span) if span < W else (0, W)
+    lon = cols.astype(np.float64) * (360.0 / W)
+    half = kx * (180.0 / W)
+    return dict(rows=rows, cols=cols, Ho=Ho, Wo=Wo, k=(ky, kx), grid=(H, W), src_box=(sr0, sr1, sc0, snc), row0=row0, ntap=ntap, rw=rw,
+                lat_bnds=lat_bnds, lon_bnds=np.stack([lon - half, lon + half], axis=1))
+
+
+def grid_box(region, H=721, W=1440, stride=None, coarsen=None):
     """region = (lat_min, lat_max, lon_min, lon_max) in degrees -> dict(rows=(r0, r1), col0, ncols, box, lat, lon).
 
     The box holds the grid points with lat in [lat_min, lat_max] and lon in the closed eastward interval from lon_min to
@@ -66,9 +159,12 @@ def grid_box(region, H=721, W=1440, stride=None):
     decode_latent take; lat / lon (float64, lon in [0, 360)) are the coordinates of the rows / columns.
     stride (resolve_stride): lat / lon are those of the kept rows / columns only (kept_points; `box` stays the unthinned
     box) and the dict also carries stride = (s_lat, s_lon) and kept_rows / kept_cols (global indices).
-    Raises ValueError for an empty box, a latitude outside [-90, 90] or lat_min > lat_max, a bad stride, or a box in
-    which the stride keeps no row / no column."""
-    step = resolve_stride(stride, W)
+    coarsen (resolve_coarsen; not together with a stride): lat / lon, kept_rows / kept_cols are those of stride=coarsen -
+    the points the area-weighted mean is returned at - and the dict carries coarsen = (k_lat, k_lon), lat_bnds [Ho, 2]
+    (north, south) and lon_bnds [Wo, 2] (west, east), the edges of the coarse cells in degrees (coarsen_plan).
+    Raises ValueError for an empty box, a latitude outside [-90, 90] or lat_min > lat_max, a bad stride / coarsen, both
+    of them, or a box in which the stride keeps no row / no column."""
+    step, coarse = _stride_or_coarsen(stride, coarsen, H, W)
     try:
         lat_min, lat_max, lon_min, lon_max = (float(v) for v in region)
     except (TypeError, ValueError):
@@ -106,6 +202,14 @@ def grid_box(region, H=721, W=1440, stride=None):
             raise ValueError(f"region {region!r}: {e}") from None
         rows = kr.astype(np.float64)
         extra = dict(stride=step, kept_rows=kr, kept_cols=cols)
+    if coarse is not None:
+        try:
+            p = coarsen_plan((r0, r_last + 1, c0, nc), coarse, H, W)
+        except ValueError as e:
+            raise ValueError(f"region {region!r}: {e}") from None
+        cols = p["cols"]
+        rows = p["rows"].astype(np.float64)
+        extra = dict(coarsen=coarse, kept_rows=p["rows"], kept_cols=cols, lat_bnds=p["lat_bnds"], lon_bnds=p["lon_bnds"])
     return dict(rows=(r0, r_last + 1), col0=c0, ncols=nc, box=(r0, r_last + 1, c0, nc),
                 lat=90.0 - rows * (180.0 / (H - 1)), lon=cols.astype(np.float64) * (360.0 / W), **extra)
 

@@ -788,11 +788,13 @@ class VAEformer(nn.Module):
         return params[:L], params[L:]
 
     # ---- g_s --------------------------------------------------------------------------------
-    def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None):
+    def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None, coarsen=None):
         """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300).  channels / box / step (canonical, _subset_args):
         the [len(channels), r1 - r0, nc] slice of that frame - thinned to the global rows % s_lat == 0 / columns % s_lon
-        == 0 when step = (s_lat, s_lon) -, bit for bit (_unembed).  out: the contiguous destination of _decoded_shape
-        (one frame of the caller's batch result) - the un-embed writes x_hat there; None: a fresh tensor."""
+        == 0 when step = (s_lat, s_lon) -, bit for bit (_unembed).  coarsen = (k_lat, k_lon) (_coarsen_arg; not with a
+        step): the area-weighted mean of that frame at the points step = coarsen would keep (_unembed_coarsened).  out: the
+        contiguous destination of _decoded_shape (one frame of the caller's batch result) - the un-embed writes x_hat
+        there; None: a fresh tensor."""
         cfg = self.cfg
         D, L = cfg['embed_dim'], cfg['latent_dim']
         N = self.Hp * self.Wp
@@ -806,7 +808,7 @@ class VAEformer(nn.Module):
         Cout, (Himg, Wimg) = cfg['out_chans'], cfg['img_size']
         # the LayerNorm writes plain rows when the whole frame's un-embed would take them (a subset's geometry may not)
         h = self._ln(t, self.g_s.norm, f"h{D}", plain=self._fused_unembed_form(Cout, Himg, Wimg)[1])
-        return self._unembed(h, mean, std, channels, box, step, out)
+        return self._unembed(h, mean, std, channels, box, step, out, coarsen=coarsen)
 
     # ---- un-embed: the whole frame, or chosen channels and / or a lat-lon box of it ---------------------------
     # The transformer runs on the whole grid (global attention); everything after the final LayerNorm is local.  The
@@ -849,6 +851,38 @@ class VAEformer(nn.Module):
             subset.kept_points(box if box is not None else (0, H, 0, W), step, W)
         return step
 
+    def _coarsen_arg(self, coarsen, box, step=None):
+        """Validate a coarsening factor (int | (k_lat, k_lon) | None) for the canonical `box` of _subset_args ->
+        (k_lat, k_lon), or None for none (None, 1, (1, 1): the path without it, unchanged).  ValueError for a bad factor
+        (subset.resolve_coarsen), together with a step (_step_arg's canonical value), or a box that holds no output point."""
+        H, W = self.cfg['img_size']
+        k = subset.resolve_coarsen(coarsen, H, W)
+        if k is not None:
+            if step is not None:
+                raise ValueError(f"stride {step!r} and coarsen {k!r}: pass one of the two")
+            subset.kept_points(box if box is not None else (0, H, 0, W), k, W)
+        return k
+
+    def _coarsen_tables(self, box, k):
+        """(subset.coarsen_plan, ops.coarsen_tables) of the canonical box and factor - built once per (box, k), cached
+        like the stride tables."""
+        H, W = self.cfg['img_size']
+
+        def make():
+            p = subset.coarsen_plan(box, k, H, W)
+            return p, ops.coarsen_tables(p, self.device)
+        return self._sub_cached(("cplan", self.device, box, k), self, make)
+
+    def coarsen_frame(self, x, coarsen, out=None):
+        """The area-weighted mean (subset.coarsen_plan, ops.coarsen) of a whole frame x [C, H, W] (contiguous fp32, on the
+        model's device) -> [C, Ho, Wo]: what a decode with coarsen= returns, applied to a frame already on the device
+        (the truth frame of an evaluation)."""
+        self._require_gpu()
+        k = self._coarsen_arg(coarsen, None)
+        if k is None:
+            raise ValueError("coarsen_frame: coarsen must be a factor > 1 in at least one dimension")
+        return ops.coarsen(x, self._coarsen_tables(None, k)[1], out=out)
+
     def _sub_cached(self, key, src, make):
         """Entry `key` of the bounded subset cache, rebuilt by `make()` when `src` (the tensor / derived weight it was
         made from) is no longer the one it holds."""
@@ -886,8 +920,10 @@ class VAEformer(nn.Module):
         return self._sub_cached(("stat", t.data_ptr(), t._version, chans), t,
                                 lambda: t.index_select(0, torch.tensor(chans, device=t.device, dtype=torch.long)))
 
-    def _decoded_shape(self, channels=None, box=None, step=None):
-        """[C', H', W'] of one decoded frame for the canonical channels / box (_subset_args) and step (_step_arg)."""
+    def _decoded_shape(self, channels=None, box=None, step=None, coarsen=None):
+        """[C', H', W'] of one decoded frame for the canonical channels / box (_subset_args) and step (_step_arg) or
+        coarsen (_coarsen_arg: the shape of step = coarsen)."""
+        step = step if coarsen is None else coarsen
         H, W = self.cfg['img_size']
         C = len(channels) if channels is not None else self.cfg['out_chans']
         r0, r1, _, nc = box if box is not None else (0, H, 0, W)
@@ -919,13 +955,15 @@ class VAEformer(nn.Module):
                  if self.gemm_mode == "split" and self.fused_unembed and D <= 8192 else 0)
         return nside, bool(nside) and self._hi("g_s.final") and self.f16_layout == "plain" and D % 64 == 0
 
-    def _unembed(self, h, mean, std, chans, box, step=None, out=None):
+    def _unembed(self, h, mean, std, chans, box, step=None, out=None, coarsen=None):
         """The un-embed for channels `chans` (tuple | None: all) inside grid box `box` (tuple | None: the whole grid),
         from the final LayerNorm's output h (SplitMat, or fp32 [N, D] on the exact-f32 engines) -> [C', Hb, Wb], written
         into `out` (_frame_dest: a frame of the caller's batch result - every form below stores straight into it; None:
         a fresh tensor).  chans = box = None is the full decode.  step = (s_lat, s_lon): only the box's points on the
         global lattice rows % s_lat == 0, columns % s_lon == 0 -> [C', Ho, Wo] (_unembed_thinned: the same products, far
-        fewer)."""
+        fewer).  coarsen = (k_lat, k_lon): _unembed_coarsened."""
+        if coarsen is not None:
+            return self._unembed_coarsened(h, mean, std, chans, box, coarsen, out)
         if step is not None:
             return self._unembed_thinned(h, mean, std, chans, box, step, out)
         cfg = self.cfg
@@ -1062,6 +1100,22 @@ class VAEformer(nn.Module):
         out = self._frame_dest(out, (Cs, p["Ho"], p["Wo"]))
         return ops.strided_scatter(g, tdev["rows"], tdev["cols"], tdev["cls"], tb["n_cc"], Cs, mean=ms, std=ss, out=out)
 
+    def _unembed_coarsened(self, h, mean, std, chans, box, k, out=None):
+        """_unembed with a coarsening factor k = (k_lat, k_lon): the un-embed runs unthinned on the source box the
+        windows need (subset.coarsen_plan: the box's kept points grown by k // 2 rows / columns, the whole circle when it
+        closes) into a per-thread persistent buffer - de-normalised when mean / std are given: x * std + mean is affine
+        per channel, so the weighted mean of the de-normalised values IS what coarsening the full decode returns - and
+        ONE streaming kernel (ops.coarsen, csrc/coarsen.hip) writes the area-weighted means into `out`.  The source
+        buffer holds exactly the values (bits) the full decode has there (_unembed: the subset decode's guarantee)."""
+        H, W = self.cfg['img_size']
+        plan, tdev = self._coarsen_tables(box, k)
+        sb = tuple(int(v) for v in plan["src_box"])
+        Cs = len(chans) if chans is not None else self.cfg['out_chans']
+        src = self._buf("ue_coarse_src", (Cs, sb[1] - sb[0], sb[3]))
+        self._unembed(h, mean, std, chans, None if sb == (0, H, 0, W) else sb, None, out=src)
+        out = self._frame_dest(out, (Cs, plan["Ho"], plan["Wo"]))
+        return ops.coarsen(src, tdev, out=out)
+
     # ---- latent side: everything between y and the entropy coder ---------------------------
     def _latent_side_frame(self, y, want_lik=False, z_sym_out=None):
         z = self._h_a_frame(y)
@@ -1174,28 +1228,30 @@ class VAEformer(nn.Module):
             return y, self._finite(flag), None
         return self._range_guard(0, run, "encode")
 
-    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None, out=None):
+    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None, out=None, coarsen=None):
         """g_s of one frame inside the caller's GPU phase -> (x_hat, pinned probe values: test them with _finite once
         the phase has ended).  The residual stream after the last block carries every upstream poison - token-wise, and
         the global attention spreads it.  The final LayerNorm's split store is O(gamma * sqrt(D)): a checkpoint with
         |gamma| sqrt(D) >= 65 504, or a non-finite mean / std, poisons x_hat BEHIND that probe - a strided sample of the
         reconstruction itself (every 2053rd pixel: ~14 samples of each token's 268 x 110-pixel patch, ~500 of every
         channel) is probed as well.  A subset decode (channels / box / step) probes the decoded subset itself:
-        every output channel sampled at least min(its element count, 500) times.  out: _decode_frame's destination -
-        the probe reads the frame where it was written."""
-        x_hat = self._decode_frame(y_hat, mean=mean, std=std, channels=channels, box=box, step=step, out=out)
+        every output channel sampled at least min(its element count, 500) times - a coarsened decode likewise: a
+        non-finite value of the source stays non-finite through the weighted mean of every window that holds it.  out:
+        _decode_frame's destination - the probe reads the frame where it was written."""
+        x_hat = self._decode_frame(y_hat, mean=mean, std=std, channels=channels, box=box, step=step, out=out,
+                                   coarsen=coarsen)
         D = self.cfg['embed_dim']
-        whole = channels is None and box is None and step is None
+        whole = channels is None and box is None and step is None and coarsen is None
         stride = 2053 if whole else max(1, (x_hat.numel() // x_hat.shape[0]) // 500)
         return x_hat, self._to_host("ok1", self._probe(self._buf(f"t{D}", (self.Hp * self.Wp, D)), (x_hat, stride)))
 
-    def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None):
+    def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None, coarsen=None):
         """g_s of one frame under the range guard: y_hat [L, Hp, Wp] -> x_hat [C, H, W] (or its subset: canonical
-        channels / box of _subset_args, step of _step_arg).  out: the frame's destination (_decode_frame); a re-run on
+        channels / box of _subset_args, step of _step_arg or coarsen of _coarsen_arg).  out: the frame's destination (_decode_frame); a re-run on
         the exact-f32 engines overwrites the same destination."""
         def run():
             with self._gpu_phase():
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, run, "decode")
 
@@ -1226,20 +1282,25 @@ class VAEformer(nn.Module):
         return y, None, None
 
     @torch.no_grad()
-    def decode_latent(self, y, type='quantized', channels=None, box=None, step=None):
+    def decode_latent(self, y, type='quantized', channels=None, box=None, step=None, coarsen=None):
         """vaeformer.py:294-300.  channels: output channel indices (in the order given); box = (r0, r1, c0, nc): grid rows
         [r0, r1) and nc columns from c0, wrapping at W (subset.grid_box) -> [B, len(channels), r1 - r0, nc], the same
         slice of the full decode bit for bit.  step: a stride, int | (s_lat, s_lon) - of the box (default: the globe) only
         the rows r with r % s_lat == 0 and the columns c with c % s_lon == 0 (GLOBAL indices; subset.kept_points), again
         bit for bit: with `full` the full decode under the same engines and precision, the result equals
-        full[channels][:, kept_rows][:, :, kept_cols] as bit patterns.  None / 1 / (1, 1): no thinning."""
+        full[channels][:, kept_rows][:, :, kept_cols] as bit patterns.  None / 1 / (1, 1): no thinning.
+        coarsen: int | (k_lat, k_lon), not together with a step - at the points step = coarsen keeps, the area-weighted
+        mean of the full decode over the coarse cell round each (first-order conservative; subset.coarsen_plan, DESIGN.md
+        section 4): fixed float64 arithmetic, a region's result is the sub-block of the globe's bit for bit."""
         self._require_gpu()
         channels, box = self._subset_args(channels, box)
         step = self._step_arg(step, box)
+        coarsen = self._coarsen_arg(coarsen, box, step)
         # the batch result is allocated once and every frame's un-embed stores into its slice (no stack copy)
-        out = torch.empty((y.shape[0],) + self._decoded_shape(channels, box, step), device=self.device, dtype=torch.float32)
+        out = torch.empty((y.shape[0],) + self._decoded_shape(channels, box, step, coarsen), device=self.device,
+                          dtype=torch.float32)
         for b in range(y.shape[0]):
-            self._decode_guarded(y[b], channels=channels, box=box, step=step, out=out[b])
+            self._decode_guarded(y[b], channels=channels, box=box, step=step, out=out[b], coarsen=coarsen)
         return out
 
     @torch.no_grad()
@@ -1379,10 +1440,10 @@ class VAEformer(nn.Module):
             "stream or a different checkpoint looks the same.  Nothing was reconstructed", e.status)
 
     def _decompress_frame(self, y_string, z_string, shape, reconstruct, mean=None, std=None, channels=None, box=None,
-                          step=None, out=None):
+                          step=None, out=None, coarsen=None):
         """host: decode z | GPU: h_s, indexes | host: decode y | GPU: de-quantise (+ g_s: the whole frame, or the
-        canonical channels / box of _subset_args, step of _step_arg; out: the reconstruction's destination,
-        _decode_frame)."""
+        canonical channels / box of _subset_args, step of _step_arg or coarsen of _coarsen_arg; out: the
+        reconstruction's destination, _decode_frame)."""
         eb, gc = self.entropy_bottleneck, self.gaussian_conditional
         Cz = eb.channels
         zh, zw = int(shape[0]), int(shape[1])
@@ -1457,31 +1518,32 @@ class VAEformer(nn.Module):
                     y_hat = ops.gaussian_conditional(scales, means, gc.scale_table, sym_in=y_sym, want=("y_hat",))["y_hat"]
                 if not reconstruct:
                     return y_hat, True, None
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, gpu_side, "decompress")
 
     @torch.no_grad()
-    def decompress(self, strings, shape, return_format='reconstructed', channels=None, box=None, step=None):
-        """vaeformer.py:378-400.  channels / box / step: a subset of the reconstruction (decode_latent)."""
+    def decompress(self, strings, shape, return_format='reconstructed', channels=None, box=None, step=None, coarsen=None):
+        """vaeformer.py:378-400.  channels / box / step / coarsen: a subset of the reconstruction (decode_latent)."""
         self._require_gpu()
         assert isinstance(strings, list) and len(strings) == 2
         rec = return_format != 'latent'
-        if not rec and (channels is not None or box is not None or step is not None):
-            raise ValueError("decompress: return_format='latent' returns the latent; channels / box / step select a "
-                             "subset of the reconstruction")
+        if not rec and (channels is not None or box is not None or step is not None or coarsen is not None):
+            raise ValueError("decompress: return_format='latent' returns the latent; channels / box / step / coarsen "
+                             "select a subset of the reconstruction")
         channels, box = self._subset_args(channels, box)
         step = self._step_arg(step, box)
+        coarsen = self._coarsen_arg(coarsen, box, step)
         self.entropy_bottleneck._check()
         self.gaussian_conditional._check()
         B = len(strings[0])
         if not rec:
             return torch.stack([self._decompress_frame(strings[0][b], strings[1][b], shape, False) for b in range(B)])
         # the batch result is allocated once and every frame's un-embed stores into its slice (no stack copy)
-        out = torch.empty((B,) + self._decoded_shape(channels, box, step), device=self.device, dtype=torch.float32)
+        out = torch.empty((B,) + self._decoded_shape(channels, box, step, coarsen), device=self.device, dtype=torch.float32)
         for b in range(B):
             self._decompress_frame(strings[0][b], strings[1][b], shape, True, channels=channels, box=box, step=step,
-                                   out=out[b])
+                                   out=out[b], coarsen=coarsen)
         return {"x_hat": out}
 
     @torch.no_grad()

@@ -302,6 +302,27 @@ int cra5_strided_scatter_f32(const float *g, size_t g_elems, const int *rows, co
                              int n_rc, int n_cc, const float *mean, const float *stdv, float *x, int C, int Ho, int Wo,
                              void *stream);
 
+/* Area-weighted coarsening (csrc/coarsen.hip; cra5_amd/subset.py coarsen_plan): the first-order
+ * conservative regrid of src - fp32 [C_src][Hs][Ws], contiguous, whose element [.][0][0] is the GLOBAL grid point (src_r0,
+ * src_c0) of an H x W grid; whole_circle != 0: Ws == W and src_c0 == 0, windows wrap at the east edge - onto the Ho x Wo
+ * points of global rows out_r0 + i * k_lat and global columns (out_c0 + j * k_lon) mod W -> dst fp32 [C_out][Ho][Wo],
+ * contiguous.  Output channel c reads source channel chan_map[c] (int32 [C_out] on the device) or c when chan_map is NULL
+ * (then C_out <= C_src); a mapped channel outside [0, C_src) gives NaN.  Device tables: row0 / ntap int32 [Ho] - the first
+ * global source row and the row count (<= rw_pitch) of output row i's window; rw fp64 [Ho][rw_pitch] - its row weights.
+ * Per output point, in fp64, every operation rounded on its own (no contraction):
+ *   acc = 0;  for t < ntap[i], north to south:  inner = 0;  for w = col - k_lon / 2 .. col + k_lon / 2 (mod W), west to
+ *   east:  inner = inner + ov * (double)src[row0[i] + t][w]  (ov = 1/2 on the two edge columns of an even k_lon, else 1);
+ *   acc = acc + rw[i][t] * inner;   dst = (float)acc.
+ * The order depends on the global (row, column) only: a region's result is the sub-block of the globe's, bit for bit.
+ * Non-finite samples propagate (IEEE); nothing is filtered.  One pass, no atomics, 64-bit element offsets; any 4-byte
+ * aligned src / dst.  A table row outside the source is not read: the output row becomes NaN.  CRA5_ERR_ARG, before any
+ * device work, for NULL / misaligned pointers (chan_map may be NULL), sizes <= 0, a source box outside the grid, a
+ * whole-circle flag on another box, Wo * k_lon > W, output rows beyond H - 1, a window (out_r0 - k_lat / 2 .. last row +
+ * k_lat / 2 clipped to the grid; out_c0 - k_lon / 2 .. eastward) that leaves the source, and k_lon > 8175. */
+int cra5_coarsen_f32(const float *src, int C_src, int Hs, int Ws, int src_r0, int src_c0, int H, int W, int whole_circle,
+                     int out_r0, int k_lat, int Ho, int out_c0, int k_lon, int Wo, const int *row0, const int *ntap,
+                     const double *rw, int rw_pitch, const int *chan_map, int C_out, float *dst, void *stream);
+
 /* Finiteness probe of the range guard: partials[b] = sum of x[i * stride] over block b's share of i = 0 .. ceil(n / stride)
  * - 1, b = 0 .. CRA5_PROBE_PARTIALS - 1 (written, never accumulated: no memset, deterministic).  A partial is non-finite as
  * soon as one addend is; the caller copies the partials to the host with the phase's other results and tests them there. */

@@ -1,0 +1,360 @@
+"""Area-weighted coarsening on the GPU (cra5_coarsen_f32 / ops.coarsen, VAEformer coarsen=, cra5_api coarsen=): every
+value against the sequential float64 numpy loop of tests/coarsen_helpers.py, bit for bit."""
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+import coarsen_helpers as ch
+from time_stats_helpers import ref_time_stats
+from cra5_amd import metrics, ops, subset, synth
+from cra5_amd._lib import Cra5Error
+from cra5_amd.api import cra5_api
+from cra5_amd.vaeformer import VAEformer
+
+pytestmark = pytest.mark.gpu
+
+H, W = 721, 1440
+GRIDS = [(13, 24), (25, 40), (7, 1440)]
+KS = [(2, 2), (3, 3), (4, 4), (6, 6), (12, 8), (1, 4), (6, 1), (2, 3)]
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
+def _field(C, Hg, Wg, seed, physical=True):
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((C, Hg, Wg))
+    if physical:
+        x = 5e4 * (1 + 0.2 * rng.random((C, 1, 1))) + 1e4 * x
+    return x.astype(np.float32)
+
+
+def _source(full, plan):
+    """The plan's source box cut out of the global field (columns wrap)."""
+    sr0, sr1, sc0, snc = plan["src_box"]
+    return np.ascontiguousarray(full[:, sr0:sr1][:, :, (sc0 + np.arange(snc)) % full.shape[2]])
+
+
+def _boxes(Hg, Wg, k):
+    """The globe, an interior box, a box on each pole, a box across 0 deg, a single output point."""
+    return [None, (Hg // 4, Hg // 4 + Hg // 2, Wg // 8, Wg // 2), (0, Hg // 2, 3, Wg // 3), (Hg // 2, Hg, 5, Wg // 3),
+            (1, Hg - 1, Wg - Wg // 6, Wg // 3), (k[0], k[0] + 1, k[1] % Wg, 1)]
+
+
+def _run(full, k, box, dev, chan_map=None, off_src=0, off_dst=0):
+    C, Hg, Wg = full.shape
+    plan = subset.coarsen_plan(box, k, Hg, Wg)
+    t = ops.coarsen_tables(plan, dev)
+    src = _source(full, plan)
+    sbuf = torch.full((src.size + 4,), -3.0, device=dev)
+    sbuf[off_src:off_src + src.size].copy_(torch.from_numpy(src).reshape(-1))
+    xs = sbuf[off_src:off_src + src.size].view(src.shape)
+    Co = C if chan_map is None else len(chan_map)
+    n = Co * plan["Ho"] * plan["Wo"]
+    dbuf = torch.full((n + 12,), -7.0, device=dev)
+    lo = 4 + off_dst                       # guard words in front; `out` starts 4 * off_dst bytes past a 16-byte boundary
+    out = dbuf[lo:lo + n].view(Co, plan["Ho"], plan["Wo"])
+    assert sbuf.data_ptr() % 16 == 0 and dbuf.data_ptr() % 16 == 0
+    assert xs.data_ptr() % 16 == 4 * off_src and out.data_ptr() % 16 == 4 * off_dst
+    cm = None if chan_map is None else torch.tensor(chan_map, device=dev, dtype=torch.int32)
+    got = ops.coarsen(xs, t, out=out, chan_map=cm)
+    assert got is out
+    assert (dbuf[:lo] == -7.0).all() and (dbuf[lo + n:] == -7.0).all()      # nothing written around the result
+    return out.cpu().numpy()
+
+
+@pytest.mark.parametrize("grid", GRIDS)
+@pytest.mark.parametrize("C", [1, 3])
+def test_kernel_equals_the_sequential_float64_loop(dev, grid, C):
+    Hg, Wg = grid
+    n_cases = single = 0
+    for physical in (True, False):                      # zero-mean data: cancellation shows a wrong summation order
+        full = _field(C, Hg, Wg, seed=Hg + C, physical=physical)
+        for k in KS:
+            if (Hg - 1) % k[0] or Wg % k[1]:
+                continue
+            for box in _boxes(Hg, Wg, k):
+                try:
+                    subset.kept_points(box if box is not None else (0, Hg, 0, Wg), k, Wg)
+                except ValueError:
+                    continue
+                ref = ch.ref_coarsen(full, k, box)
+                got = _run(full, k, box, dev)
+                assert np.array_equal(got, ref, equal_nan=True) and _same_bits(got, ref), (grid, C, physical, k, box)
+                n_cases += 1
+                single += ref.shape[1:] == (1, 1)
+    assert n_cases >= 20 and single >= 1
+
+
+def test_kernel_chan_map_alignment_nonfinite_and_sub_block(dev):
+    Hg, Wg, k = 25, 40, (4, 4)
+    full = _field(5, Hg, Wg, seed=9)
+    # chan_map: a reordered variable subset of the full source, no gather
+    got = _run(full, k, None, dev, chan_map=[4, 0, 2])
+    assert _same_bits(got, ch.ref_coarsen(full, k, None, chans=[4, 0, 2]))
+    # source and destination 4 and 12 bytes off a 16-byte boundary
+    ref = ch.ref_coarsen(full, k, (3, 22, 30, 25))
+    for off_src, off_dst in ((1, 3), (3, 1), (1, 1), (3, 3)):
+        assert _same_bits(_run(full, k, (3, 22, 30, 25), dev, off_src=off_src, off_dst=off_dst), ref), (off_src, off_dst)
+    # NaN and +inf in an edge column two outputs share (column 4 j + 2) - and an edge row two output rows share (row 4 i + 2)
+    bad = full.copy()
+    bad[1, 10, 6] = np.nan
+    bad[3, 14, 38] = np.inf
+    bad[0, 0, 2] = -np.inf
+    ref = ch.ref_coarsen(bad, k)
+    got = _run(bad, k, None, dev)
+    assert np.array_equal(got, ref, equal_nan=True)
+    assert np.isnan(got[1]).sum() == 4 and np.isnan(ref[1, 2:4, 1:3]).all() and np.isposinf(got[3]).sum() == 4
+    assert np.isneginf(got[0, 0, 0:2]).all() and np.isfinite(got[2]).all() and np.isfinite(got[4]).all()
+    # a region's result is the sub-block of the globe's, as bit patterns
+    for kk in [(4, 4), (6, 5), (3, 8)]:
+        glob = _run(full, kk, None, dev)
+        grows, gcols = ch.kept(None, kk, Hg, Wg)
+        for box in _boxes(Hg, Wg, kk)[1:]:
+            rows, cols = ch.kept(box, kk, Hg, Wg)
+            ii = [list(grows).index(r) for r in rows]
+            jj = [list(gcols).index(c) for c in cols]
+            sub = _run(full, kk, box, dev)
+            assert np.array_equal(sub.view(np.int32), glob[:, ii][:, :, jj].view(np.int32)), (kk, box)
+
+
+def test_ops_argument_checks(dev):
+    Hg, Wg, k = 13, 24, (6, 6)
+    full = _field(2, Hg, Wg, seed=1)
+    plan = subset.coarsen_plan((0, 13, 6, 7), k, Hg, Wg)            # columns 6 and 12: source columns 3 .. 15
+    t = ops.coarsen_tables(plan, dev)
+    x = torch.from_numpy(_source(full, plan)).to(dev)
+    assert _same_bits(ops.coarsen(x, t).cpu().numpy(), ch.ref_coarsen(full, k, (0, 13, 6, 7)))
+    with pytest.raises(ValueError, match="source box"):
+        ops.coarsen(x[:, :, :-1].contiguous(), t)
+    with pytest.raises(ValueError, match="out must be"):
+        ops.coarsen(x, t, out=torch.empty((2, 3, 3), device=dev))
+    with pytest.raises(ValueError, match="chan_map"):
+        ops.coarsen(x, t, chan_map=torch.tensor([0], device=dev))                   # int64
+    with pytest.raises(ValueError, match="coarsen_tables"):
+        ops.coarsen(x, plan)                                                        # host tables
+    with pytest.raises(RuntimeError):
+        ops.coarsen(x.cpu(), t)
+    # the launcher's own checks (CRA5_ERR_ARG = -7): a window that leaves the source; Wo * k_lon > W; rows beyond the grid
+    for key, val, xs in (("src_box", (0, 13, 4, 12), x[:, :, 1:].contiguous()),      # source starts one column too far east
+                         ("src_box", (1, 13, 3, 13), x[:, 1:].contiguous()),         # the north pole's window row is missing
+                         ("k", (6, 24), x), ("grid", (12, 24), x)):
+        t2 = dict(t)
+        t2[key] = val
+        with pytest.raises(Cra5Error) as e:
+            ops.coarsen(xs, t2)
+        assert e.value.status == -7, (key, val)
+    # a mapped channel outside the source gives NaN, nothing is read
+    cm = torch.tensor([1, 2], device=dev, dtype=torch.int32)
+    got = ops.coarsen(x, t, chan_map=cm)
+    assert torch.isnan(got[1]).all() and _same_bits(got[0].cpu().numpy(), ch.ref_coarsen(full, k, (0, 13, 6, 7))[1])
+
+
+# ---- the model ---------------------------------------------------------------------------------------------------------
+
+
+def _yhat(latent, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.round(2.0 * torch.randn(1, latent, 72, 144, generator=g)) + torch.randn(1, latent, 72, 144, generator=g)
+
+
+def _thin(dev, mod=None):
+    net = VAEformer(0, **synth.thin_model_kwargs())
+    synth.load_synthetic(net, seed=7)
+    if mod is not None:
+        with torch.no_grad():
+            mod(net)
+    return net.to(dev)
+
+
+@pytest.fixture(scope="module")
+def thin(dev):
+    return _thin(dev)
+
+
+@pytest.fixture(scope="module")
+def latent(dev):
+    return _yhat(16, seed=11).to(dev)
+
+
+MODEL_KS = [(2, 2), (5, 5), (6, 6), (8, 10), (6, 1)]
+MODEL_BOXES = [None, (72, 221, 1340, 281), (690, 721, 200, 333)]      # the globe, Europe across 0 deg, a box on row 720
+MODEL_CHANS = [None, [6], [5, 1, 3]]
+
+
+@pytest.mark.parametrize("engine", ["default", "f32"])
+def test_coarsened_decode_equals_the_helper_on_the_full_decode(thin, latent, dev, engine):
+    keep = thin.gemm_mode
+    try:
+        if engine == "f32":
+            thin.gemm_mode = "f32"
+        mean = torch.linspace(-1, 1, 8, device=dev)
+        std = torch.linspace(0.5, 2, 8, device=dev)
+        full_n = thin.decode_latent(latent)[0].cpu().numpy()
+        full_d = thin._decode_guarded(latent[0], mean=mean, std=std).cpu().numpy()
+        n = 0
+        for k in MODEL_KS:
+            for b, box in enumerate(MODEL_BOXES):
+                chans = MODEL_CHANS[(n + b) % 3]
+                denorm = (n + b) % 2 == 0
+                if denorm:
+                    c_, b_ = thin._subset_args(chans, box)
+                    got = thin._decode_guarded(latent[0], mean=mean, std=std, channels=c_, box=b_,
+                                               coarsen=thin._coarsen_arg(k, b_))
+                else:
+                    got = thin.decode_latent(latent, channels=chans, box=box, coarsen=k)[0]
+                ref = ch.ref_coarsen(full_d if denorm else full_n, k, box, chans)
+                assert _same_bits(got.cpu().numpy(), ref), (engine, k, box, chans, denorm)
+            n += 1
+        # an int is the pair; 1 / (1, 1) / None are the path without it; a plain decode afterwards is unchanged
+        assert _same_bits(thin.decode_latent(latent, coarsen=6)[0].cpu().numpy(), ch.ref_coarsen(full_n, (6, 6)))
+        for same in (None, 1, (1, 1)):
+            assert _same_bits(thin.decode_latent(latent, coarsen=same)[0].cpu().numpy(), full_n)
+        assert _same_bits(thin.decode_latent(latent, channels=[5, 1, 3], box=MODEL_BOXES[1])[0].cpu().numpy(),
+                          full_n[[5, 1, 3], 72:221][:, :, (1340 + np.arange(281)) % W])
+        assert thin.range_fallbacks == [0, 0]
+    finally:
+        thin.gemm_mode = keep
+
+
+def test_coarsen_argument_errors(thin, latent):
+    for bad in (0, -1, (2, 0), 2.5, "2", (2, 2, 2), True):
+        with pytest.raises(ValueError, match="coarsen"):
+            thin.decode_latent(latent, coarsen=bad)
+    with pytest.raises(ValueError, match=r"k_lat \(7\)"):
+        thin.decode_latent(latent, coarsen=7)
+    with pytest.raises(ValueError, match="one of the two"):
+        thin.decode_latent(latent, step=6, coarsen=6)
+    with pytest.raises(ValueError, match="no row"):
+        thin.decode_latent(latent, box=(1, 5, 0, 40), coarsen=6)
+    with pytest.raises(ValueError, match="latent"):
+        thin.decompress([[b""], [b""]], (18, 36), return_format="latent", coarsen=6)
+
+
+def _mod_gs(net):      # outlier hidden units in a g_s MLP (tests/test_strided_decode_gpu.py)
+    net.g_s.blocks[2].mlp.fc1.weight[:4] *= 3e5
+    net.g_s.blocks[2].mlp.fc1.bias[:4] *= 3e5
+    net.g_s.blocks[2].mlp.fc2.weight[:, :4] /= 3e5
+
+
+def test_range_guard_reruns_a_poisoned_coarsened_decode(dev, latent):
+    net = _thin(dev, _mod_gs)
+    ref = _thin(dev, _mod_gs)
+    ref.gemm_mode, ref.attn_mode = "f32", "f32"
+    full = ref.decode_latent(latent)[0].cpu().numpy()
+    assert ref.range_fallbacks == [0, 0]
+    for chans, box, k in [([6, 2], (72, 221, 1340, 281), (6, 4)), (None, None, (6, 6))]:
+        with pytest.warns(RuntimeWarning, match="exact-f32"):
+            got = net.decode_latent(latent, channels=chans, box=box, coarsen=k)[0]
+        assert torch.isfinite(got).all()
+        assert _same_bits(got.cpu().numpy(), ch.ref_coarsen(full, k, box, chans)), (chans, box, k)
+    assert net.range_fallbacks == [0, 2]
+
+
+# ---- the API -----------------------------------------------------------------------------------------------------------
+
+
+def _api(net, dev, tmp_path):
+    api = cra5_api(local_root=str(tmp_path), device="cuda", weights=net)
+    api._mean_flat = torch.linspace(-1, 1, 8, device=dev)
+    api._std_flat = torch.linspace(0.5, 2, 8, device=dev)
+    api.mean, api.std = api._mean_flat.view(8, 1, 1), api._std_flat.view(8, 1, 1)
+    return api
+
+
+@pytest.fixture(scope="module")
+def files(thin, dev, tmp_path_factory):
+    root = tmp_path_factory.mktemp("coarsen")
+    api = _api(thin, dev, root)
+    frames = [(synth.synth_frame(8, seed=s) * api.std.cpu() + api.mean.cpu()).numpy() for s in (3, 4, 5, 6)]
+    stamps = [f"2024-06-0{1 + h // 2}T{6 * (h % 2):02d}:00:00" for h in range(4)]
+    api.encode_era5_batch(stamps, data=frames, save_root=str(root / "CRA5"), workers=2)
+    fulls = [api.decode_from_bin(ts, to_host=True)["x_hat"].reshape(8, H, W) for ts in stamps]
+    return api, stamps, frames, fulls, [ch.ref_coarsen(f, (6, 6)) for f in fulls]
+
+
+def test_api_decode_from_bin_coarsen(files):
+    api, stamps, _, fulls, refs = files
+    d = api.decode_from_bin(stamps[0], coarsen=6, to_host=True)
+    g = cra5_api.grid_box((-90, 90, 0, 360), coarsen=6)
+    assert set(d) == {"x_hat", "decoding_time", "variables", "lat", "lon", "coarsen", "lat_bnds", "lon_bnds"}
+    assert d["x_hat"].shape == (8, 121, 240) and _same_bits(d["x_hat"], refs[0]) and d["coarsen"] == (6, 6)
+    assert np.array_equal(d["lat"], g["lat"]) and d["lat"][0] == 90.0 and d["lat"][-1] == -90.0 and d["lat"][1] == 88.5
+    assert np.array_equal(d["lat_bnds"], g["lat_bnds"]) and np.array_equal(d["lon_bnds"], g["lon_bnds"])
+    assert d["lat_bnds"].shape == (121, 2) and d["lat_bnds"][0].tolist() == [90.0, 89.25]
+    # variables + region, on the device, normalised; the latent route
+    names = ["z_850", "z_1000", "z_925"]
+    chans = [api.vname_to_channels[v] for v in names]
+    gb = cra5_api.grid_box((35, 72, -25, 45), coarsen=(6, 4))
+    dn = api.decode_from_bin(stamps[1], variables=names, region=(35, 72, -25, 45), coarsen=(6, 4))
+    assert dn["variables"] == names and _same_bits(dn["x_hat"].reshape(3, 25, 71).cpu().numpy(),
+                                                    ch.ref_coarsen(fulls[1], (6, 4), gb["box"], chans))
+    full_n = api.decode_from_bin(stamps[1], return_format="normalized", to_host=True)["x_hat"].reshape(8, H, W)
+    xr = api.latent_to_reconstruction(api.bin_to_latent(time_stamp=stamps[1]), variables=names[:1], coarsen=10)
+    assert xr.shape == (1, 1, 73, 144) and _same_bits(xr[0].cpu().numpy(), ch.ref_coarsen(full_n, (10, 10), None, chans[:1]))
+    for same in (1, (1, 1), None):
+        assert set(api.decode_from_bin(stamps[0], coarsen=same)) == {"x_hat", "decoding_time"}
+    with pytest.raises(ValueError, match="out"):
+        api.decode_from_bin(stamps[0], coarsen=6, out=np.empty((8, H, W), dtype=np.float32))
+    with pytest.raises(ValueError, match="latent"):
+        api.decode_from_bin(stamps[0], return_format="latent", coarsen=6)
+    with pytest.raises(ValueError, match="one of the two"):
+        api.decode_from_bin(stamps[0], stride=6, coarsen=6)
+    with pytest.raises(ValueError, match=r"k_lon \(7\)"):
+        api.decode_from_bin(stamps[0], coarsen=(6, 7))
+
+
+def test_api_decode_batch_coarsen(files):
+    api, stamps, _, _, refs = files
+    out = np.empty((4, 8, 121, 240), dtype=np.float32)
+    api.decode_batch(stamps, out=out, workers=4, coarsen=6)
+    seen = {}
+    api.decode_batch(stamps, workers=1, coarsen=6, sink=lambda i, fr: seen.__setitem__(i, (fr.shape, fr.copy())))
+    fresh1 = api.decode_batch(stamps, workers=1, coarsen=6)
+    fresh4 = api.decode_batch(stamps, workers=4, coarsen=(6, 6))
+    for i in range(4):
+        assert _same_bits(out[i], refs[i]) and seen[i][0] == (8, 121, 240)
+        assert _same_bits(seen[i][1], refs[i]) and _same_bits(fresh1[i], refs[i]) and _same_bits(fresh4[i], refs[i])
+    with pytest.raises(ValueError, match="out"):       # the shape without coarsening
+        api.decode_batch(stamps, out=np.empty((4, 8, H, W), dtype=np.float32), coarsen=6)
+    with pytest.raises(ValueError, match="one of the two"):
+        api.decode_batch(stamps, stride=2, coarsen=6)
+
+
+def test_api_aggregate_batch_coarsen(files):
+    api, stamps, _, _, refs = files
+    groups = [ts[:10] for ts in stamps]
+    res = api.aggregate_batch(stamps, stats=("mean", "max"), coarsen=6, groups=groups, workers=3)
+    assert res["groups"] == ["2024-06-01", "2024-06-02"] and res["n"].tolist() == [2, 2] and res["coarsen"] == (6, 6)
+    assert res["mean"].shape == (2, 8, 121, 240) and res["lat_bnds"].shape == (121, 2) and len(res["lon"]) == 240
+    for g in range(2):
+        ref = ref_time_stats(refs[2 * g:2 * g + 2])
+        assert _same_bits(res["mean"][g], ref["mean"]) and _same_bits(res["max"][g], ref["max"])
+    with pytest.raises(ValueError, match="one of the two"):
+        api.aggregate_batch(stamps, stride=6, coarsen=6)
+
+
+def test_api_evaluate_batch_coarsen(files, dev):
+    from test_recon_error_gpu import assert_matches, ref_stats
+    api, stamps, frames, fulls, refs = files
+    paths = [f"{api.local_root}/CRA5/{ts[:4]}/{ts}.bin" for ts in stamps]
+    reps = api.evaluate_batch(stamps[:2], data=frames[:2], bins=paths[:2], workers=2, coarsen=6)
+    g = cra5_api.grid_box((-90, 90, 0, 360), coarsen=6)
+    for i, rep in enumerate(reps):
+        truth = ch.ref_coarsen(frames[i], (6, 6))
+        t_dev = api.net.coarsen_frame(torch.from_numpy(frames[i]).to(dev), 6)
+        assert _same_bits(t_dev.cpu().numpy(), truth)
+        same = metrics.reconstruction_error(torch.from_numpy(refs[i]).to(dev), t_dev)
+        for key in ("mse", "rmse", "wrmse", "bias", "mae", "max_abs", "nonfinite"):
+            assert np.array_equal(rep[key], same[key], equal_nan=True), key
+        assert_matches(rep, ref_stats(refs[i], truth, metrics.latitude_weights(121)))
+        assert rep["coarsen"] == (6, 6) and np.array_equal(rep["lat"], g["lat"]) and np.array_equal(rep["lon"], g["lon"])
+        assert rep["compression_ratio"] == 8 * H * W * 4 / rep["bin_bytes"]
+    # the codec mode (compress + decode from memory): the same reports
+    codec = api.evaluate_batch(stamps[:1], data=frames[:1], workers=1, coarsen=(6, 6))
+    assert np.array_equal(codec[0]["rmse"], reps[0]["rmse"]) and codec[0]["coarsen"] == (6, 6)
+    assert "coarsen" not in api.evaluate_batch(stamps[:1], data=frames[:1], workers=1, coarsen=1)[0]
