@@ -4,6 +4,7 @@ independent pure-Python restatement - bit-exact streams, round trips, adversaria
 import numpy as np
 import pytest
 
+import entropy_helpers as E
 from cra5_amd import ops
 from cra5_amd._lib import Cra5Error
 from oracle import cbind, rans_py
@@ -175,7 +176,8 @@ def test_decoder_bucket_tables_wide_and_narrow_rows():
 
 
 def _np_resolve(sym, idx, cdf, lens, offs):
-    """numpy restatement of the resolve step (rans_interface.cpp:121-150)."""
+    """element-by-element restatement of the resolve step (rans_interface.cpp:121-150): the cross-check of the
+    vectorised entropy_helpers.resolve_ref, which the device kernel is held to in tests/test_entropy_ints_gpu.py"""
     sr = np.zeros(sym.size, np.uint32)
     raw = np.zeros(sym.size, np.uint32)
     esc = np.zeros(sym.size, np.uint8)
@@ -212,7 +214,9 @@ def test_resolved_encoder_writes_the_same_stream(seed):
     sym[::7] = rng.integers(-(1 << 27), 1 << 27, size=sym[::7].size)
     sym[::11] = offs[idx[::11]] + lens[idx[::11]] - 2          # exactly max_value: escape with raw = 0
     a = ops.rans_encode(sym, idx, cdf, lens, offs)
-    sr, raw, esc = _np_resolve(sym, idx, cdf, lens, offs)
+    sr, raw, esc = E.resolve_ref(sym, idx, cdf, lens, offs)[:3]
+    for got, want in zip((sr, raw, esc), _np_resolve(sym, idx, cdf, lens, offs)):
+        assert got.dtype == want.dtype and np.array_equal(got, want)
     assert ops.rans_encode_resolved(sr, raw, esc) == a
     assert ops.rans_encode_resolved(np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.uint8)) == \
         ops.rans_encode(np.zeros(0, np.int32), np.zeros(0, np.int32), cdf, lens, offs)
@@ -368,18 +372,9 @@ def test_compact_records_write_and_read_the_same_streams(seed):
     idx = rng.integers(0, 64, n).astype(np.int32)
     sym = np.round(rng.standard_normal(n) * 30).astype(np.int32)      # plenty of escapes at both ends, |payload| < 4096
     ref = ops.rans_encode(sym, idx, cdf, lens, offs)
-    # host restatement of the compact resolve (device kernel: tests/test_kernels_gpu.py)
-    max_v = (lens[idx] - 2).astype(np.int64)
-    v = sym.astype(np.int64) - offs[idx]
-    neg, big = v < 0, v >= max_v
-    raw = np.where(neg, -2 * v - 1, np.where(big, 2 * (v - max_v), 0)).astype(np.uint32)
-    vc = np.where(neg | big, max_v, v)
-    sr = ((cdf[idx, vc].astype(np.uint32) & 0xFFFF) | (((cdf[idx, vc + 1] - cdf[idx, vc]).astype(np.uint32) & 0xFFFF) << 16)).astype(np.uint32)
-    nn = np.zeros(n, np.int64)
-    for k in range(3):
-        nn += (raw >> np.uint32(4 * k)) != 0
-    assert raw.max() < 4096
-    rec = np.where(vc == max_v, ((nn + 1) << 12) | raw, 0).astype(np.uint16)
+    # host restatement of the compact resolve (device kernel: tests/test_entropy_ints_gpu.py)
+    sr, raw, _, rec, overflow = E.resolve_ref(sym, idx, cdf, lens, offs)
+    assert raw.max() < 4096 and overflow == 0
     assert ops.rans_encode_resolved_compact(sr, rec) == ref
     out16 = np.empty(n, np.int16)
     ops.rans_decode_compact(ref, idx.astype(np.uint8), cdf, lens, offs, out16)

@@ -13,6 +13,7 @@ import json
 import numpy as np
 import pytest
 
+import entropy_helpers as E
 from cra5_amd import synth
 from cra5_amd.entropy import EntropyBottleneck, GaussianConditional, get_scale_table
 from oracle import cbind
@@ -117,26 +118,16 @@ def test_reference_integers_thin_frame_a_through_the_product_coder(golden_dir):
 def test_resolved_encoder_on_the_reference_integers(golden_dir, which):
     """The frame path encodes from device-resolved records (start | range, escape payload, nibble count); the host half
     of that route (`cra5_rans_encode_resolved`) on records resolved HERE from the reference's integers must write the
-    same bytes as the one-call encoder (the device resolve kernel is held to the same records in test_kernels_gpu)."""
+    same bytes as the one-call encoder (the device resolve kernel is held to the same restatement, entropy_helpers.resolve_ref,
+    in tests/test_entropy_ints_gpu.py::test_resolve_records_match_the_reference)."""
     from cra5_amd import ops
     g = np.load(f"{golden_dir}/{which}.npz")
     idx, sym = g["idx_full"].astype(np.int32), g["sym_full"].astype(np.int32)
     gc = _gc()
     cdf, ln, off = gc.host_tables()
-    # host restatement of the device resolve kernel (csrc/elementwise.hip resolve_symbols_kernel; rans_interface.cpp
-    # :120-160): value = sym - offset, escapes at both ends carry the folded payload and its nibble count
-    max_v = (ln[idx] - 2).astype(np.int64)
-    v = sym.astype(np.int64) - off[idx]
-    neg, big = v < 0, v >= max_v
-    raw = np.where(neg, -2 * v - 1, np.where(big, 2 * (v - max_v), 0)).astype(np.uint32)
-    vc = np.where(neg | big, max_v, v)
-    start = cdf[idx, vc].astype(np.uint32) & np.uint32(0xFFFF)
-    rng = (cdf[idx, vc + 1] - cdf[idx, vc]).astype(np.uint32) & np.uint32(0xFFFF)
-    sr = (start | (rng << np.uint32(16))).astype(np.uint32)
-    nn = np.zeros(sym.size, np.int64)
-    for k in range(8):      # nn = smallest n <= 8 with raw >> 4n == 0
-        nn += (raw >> np.uint32(4 * k)) != 0
-    nib = np.where(vc == max_v, nn + 1, 0).astype(np.uint8)
+    # host restatement of the device resolve kernel (csrc/rans_resolve.h; rans_interface.cpp:120-160): value = sym - offset,
+    # escapes at both ends carry the folded payload and its nibble count
+    sr, raw, nib = E.resolve_ref(sym, idx, cdf, ln, off)[:3]
     y_res = ops.rans_encode_resolved(sr, raw, nib)
     y_one = gc.encode_symbols(sym, idx)
     assert y_res == y_one
