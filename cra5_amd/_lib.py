@@ -74,6 +74,9 @@ SIGNATURES = {
     "cra5_recon_error_slab_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cra5_recon_error_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p,
                                      c_void_p]),
+    "cra5_zonal_spectrum_slab_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cra5_zonal_spectrum_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                        c_void_p, c_void_p, c_void_p]),
     "cra5_time_accumulate_f32": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cra5_time_finish_f32": (c_int, [c_size_t, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),

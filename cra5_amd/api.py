@@ -586,12 +586,12 @@ class cra5_api:
         return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box, **sel),
                                            list(enumerate(paths)))
 
-    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, coarsen=None):
+    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, coarsen=None, spectrum=False):
         """One frame of evaluate_batch on the calling frame thread: the truth is staged once into this thread's device
         frame buffer; the reconstruction comes from the in-memory strings (bin_path None) or from `bin_path`, and only
         the per-channel statistics leave the device.  coarsen = (k_lat, k_lon): both frames are coarsened on the device
         by the same kernel (the reconstruction inside its decode, the truth by VAEformer.coarsen_frame) and compared on
-        the coarse grid."""
+        the coarse grid.  spectrum: the zonal power spectra of the same device pair join the report."""
         from . import metrics
         if bin_path is None:
             enc, x = self._encode_staged(ts, arr, save_root, write=save_root is not None)
@@ -626,16 +626,23 @@ class cra5_api:
                 raise ValueError(f"{ts}: the reconstruction is {tuple(x_hat.shape[-3:])}, the truth frame {(Ce, He, We)}")
             err = metrics.reconstruction_error(x_hat.reshape(Ce, He, We), x, lat_weights=lat_weights)
             self._log("metrics", t_m)
+            if spectrum:
+                t_s = time.perf_counter()
+                spec = metrics.zonal_spectrum(x_hat.reshape(Ce, He, We), x, lat_weights=lat_weights)
+                self._log("spectrum", t_s)
         std = self._std_flat.detach().cpu().numpy().astype(np.float64)
         rep = dict(time_stamp=ts, variables=[self.channels_to_vname.get(c, str(c)) for c in range(C)])
         rep.update(err)
         rep["rmse_norm"] = err["rmse"] / std
+        if spectrum:
+            rep.update({k: spec[k] for k in ("wavenumber", "power_truth", "power_recon", "power_error",
+                                             "resolved_wavenumber")})
         rep["bin_bytes"] = n_bytes
         rep["compression_ratio"] = C * H * W * 4 / n_bytes
         return rep
 
     def evaluate_batch(self, time_stamps, data=None, bins=None, save_root=None, workers=12, lat_weights="era5",
-                       coarsen=None):
+                       coarsen=None, spectrum=False):
         """Per-variable reconstruction error of many frames, through the frame pipeline, without copying any
         reconstruction to the host.  Truth frames: `data` (a matching list of host arrays / tensors, physical units) or
         the NetCDF files of `time_stamps`.
@@ -650,7 +657,11 @@ class cra5_api:
         coarsen=k or (k_lat, k_lon): the error at the coarse resolution (coarsen=6: 1.5 deg) - truth and reconstruction are
         both area-averaged on the device (decode_from_bin's coarsen) and compared on the [C, Ho, Wo] grid, "era5" weights
         being latitude_weights(Ho); the reports also carry coarsen, lat and lon of that grid.  compression_ratio stays
-        that of the full frame."""
+        that of the full frame.
+        spectrum=True: every report also carries the zonal power spectra of metrics.zonal_spectrum on the same device
+        pair (with coarsen=, the coarse pair): wavenumber int64 [K], power_truth / power_recon / power_error float64
+        [C, K] and resolved_wavenumber int64 [C]; only the spectra leave the device.  The compared width (W, or the coarse
+        Wo) must have no prime factor above 5."""
         self.net._require_gpu()
         H, W = self.net.cfg['img_size']
         k = self.net._coarsen_arg(coarsen, None)
@@ -658,12 +669,18 @@ class cra5_api:
         if k is not None:
             g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W, coarsen=k)
             extra = dict(coarsen=k, lat=g["lat"], lon=g["lon"])
+        if spectrum:
+            Wc = W if k is None else self.net._decoded_shape(None, None, coarsen=k)[-1]
+            if not ops.spectrum_width_ok(Wc):
+                raise ValueError(f"evaluate_batch(spectrum=True): the compared width {Wc} is not supported - the row "
+                                 f"transform takes 2 <= W <= {ops.SPECTRUM_MAX_W} with no prime factor above 5")
         n = len(time_stamps)
         frames = list(data) if data is not None else [None] * n
         if len(frames) != n or (bins is not None and len(bins) != n):
             raise ValueError("evaluate_batch: time_stamps, data and bins must have the same length")
         paths = list(bins) if bins is not None else [None] * n
-        reps = self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights, k),
+        reps = self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights, k,
+                                                                         bool(spectrum)),
                                            list(zip(time_stamps, frames, paths)))
         for r in reps:
             r.update(extra)

@@ -771,6 +771,64 @@ def recon_error(x_hat, x, lat_w=None, out=None):
     return out
 
 
+SPECTRUM_MAX_W = 1440    # CRA5_SPECTRUM_MAX_W
+_TWIDDLES = {}           # (W, device) -> fp64 device [W, 2]: (cos, sin) of -2 pi j / W
+
+
+def spectrum_width_ok(W):
+    """W is a width cra5_zonal_spectrum_f32 transforms: 2 <= W <= SPECTRUM_MAX_W with no prime factor above 5."""
+    W = int(W)
+    if not 2 <= W <= SPECTRUM_MAX_W:
+        return False
+    for p in (2, 3, 5):
+        while W % p == 0:
+            W //= p
+    return W == 1
+
+
+def _twiddles(W, device):
+    key = (W, str(device))
+    t = _TWIDDLES.get(key)
+    if t is None:
+        a = -2.0 * np.pi * np.arange(W, dtype=np.float64) / W
+        t = _TWIDDLES[key] = torch.from_numpy(np.stack([np.cos(a), np.sin(a)], axis=1)).to(device)
+    return t
+
+
+def zonal_spectrum(x_hat, x, lat_w=None, out=None):
+    """cra5_zonal_spectrum_f32: zonal power spectra of the truth x, the reconstruction x_hat and d = x_hat - x (both
+    contiguous fp32 device tensors [C, H, W]; lat_w: contiguous fp32 device [H] or None) -> (power, nonfinite): fp64
+    device tensors [3, C, K] (P_x, P_x_hat, P_d; K = W // 2 + 1) and [C], both views of `out`, one flat fp64 device tensor
+    of 3 * C * K + C elements (allocated when None), so that one copy brings everything to the host.  On the current
+    stream; the twiddle table is cached per (W, device), the slab of partials comes from torch's caching allocator."""
+    ts = (x_hat, x) + ((lat_w,) if lat_w is not None else ())
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts):
+        raise TypeError("zonal_spectrum takes contiguous fp32 device tensors")
+    if x_hat.dim() != 3 or tuple(x_hat.shape) != tuple(x.shape) or x_hat.device != x.device:
+        raise ValueError(f"zonal_spectrum: x_hat {tuple(x_hat.shape)} and x {tuple(x.shape)} must be [C, H, W] of one "
+                         "shape on one device")
+    C, H, W = x.shape
+    if lat_w is not None and (tuple(lat_w.shape) != (H,) or lat_w.device != x.device):
+        raise ValueError(f"zonal_spectrum: lat_w must be [{H}] on the frames' device")
+    if not spectrum_width_ok(W):
+        raise ValueError(f"zonal_spectrum: W = {W} is not supported: the row transform takes 2 <= W <= {SPECTRUM_MAX_W} "
+                         "with no prime factor above 5")
+    nb = lib().cra5_zonal_spectrum_slab_bytes(C, H, W)
+    if nb == 0:
+        raise ValueError(f"zonal_spectrum: unsupported frame shape {(C, H, W)}")
+    K = W // 2 + 1
+    if out is None:
+        out = torch.empty((3 * C * K + C,), device=x.device, dtype=torch.float64)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+              and tuple(out.shape) == (3 * C * K + C,) and out.device == x.device):
+        raise TypeError(f"zonal_spectrum: out must be a contiguous fp64 tensor [{3 * C * K + C}] on the frames' device")
+    slab = torch.empty((nb // 8,), device=x.device, dtype=torch.float64)
+    power, nonfinite = out[:3 * C * K].view(3, C, K), out[3 * C * K:]
+    check(lib().cra5_zonal_spectrum_f32(_p(x_hat), _p(x), C, H, W, _p(lat_w), _p(_twiddles(W, x.device)), _p(slab), nb,
+                                        _p(power), _p(nonfinite), _stream()), "cra5_zonal_spectrum_f32")
+    return power, nonfinite
+
+
 TIME_ACCUMULATORS = (("sum", torch.float64), ("sumsq", torch.float64), ("min", torch.float32), ("max", torch.float32))
 
 

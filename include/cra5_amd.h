@@ -349,6 +349,25 @@ size_t cra5_recon_error_slab_bytes(int C, int H, int W);
 int cra5_recon_error_f32(const float *x_hat, const float *x, int C, int H, int W, const float *lat_w, double *slab,
                          size_t slab_bytes, double *out, void *stream);
 
+/* Zonal power spectra of a frame pair (csrc/spectrum.hip): x_hat, x [C][H][W] fp32, d = x_hat - x in
+ * fp32.  For a row f(c, h, .):  F(c, h, k) = sum_w f(c, h, w) e^(-2 pi i k w / W),  k = 0 .. K - 1,  K = W / 2 + 1, and
+ *   P_f(c, k) = (1 / H) sum_h L(h) m_k |F(c, h, k)|^2 / W^2,   m_k = 1 for k = 0 and for k = W / 2 of an even W, else 2,
+ * L(h) = (double)lat_w[h] (fp32 [H]; NULL: 1); every operation after the fp32 subtraction is float64.  sum_k P_f(c, k) =
+ * mean_(h,w) L(h) f^2 (Parseval): sum_k P_d is the WMSE of cra5_recon_error_f32.  out [3][C][K] fp64: P_x, P_x_hat, P_d.
+ * nonfinite [C] fp64: the count of (h, w) where x or x_hat is NaN / +-inf, as CRA5_RECON_NONFINITE; such a channel has NaN
+ * in every bin of its three spectra, the other channels are unaffected.  W >= 2 with no prime factor above 5, W <=
+ * CRA5_SPECTRUM_MAX_W.  twiddle: device fp64 [W][2], (cos, sin) of -2 pi j / W, 16-byte aligned.  `slab`: caller-owned
+ * device scratch of >= cra5_zonal_spectrum_slab_bytes(C, H, W) bytes (one partial per block, overwritten: no memset).  16-byte
+ * aligned frames with W % 4 == 0 take the float4 path, any other 4-byte aligned frames go element by element.  Two launches
+ * on `stream`, no atomics, fixed order of operations: bit-identical from run to run.  slab_bytes returns 0 for bad
+ * dimensions (C in 1 .. 65535, H > 0, H * W < 2^31, an unsupported W); the launcher returns CRA5_ERR_ARG, before any device
+ * work, for those, for NULL / misaligned pointers (lat_w may be NULL) and for a slab that is too small. */
+#define CRA5_SPECTRUM_MAX_W 1440
+size_t cra5_zonal_spectrum_slab_bytes(int C, int H, int W);
+int cra5_zonal_spectrum_f32(const float *x_hat, const float *x, int C, int H, int W, const float *lat_w,
+                            const double *twiddle, double *slab, size_t slab_bytes, double *out, double *nonfinite,
+                            void *stream);
+
 /* Per-grid-point statistics over many frames (csrc/timestats.hip): flat fp32 frames x of n elements, accumulators of the
  * same n elements - sum / sumsq fp64, mn / mx fp32.  Each accumulator pointer may be NULL (that statistic is not kept: it
  * is neither read nor written); at least one is given.  Per element i, v = (double)x[i]:
