@@ -80,6 +80,16 @@ SIGNATURES = {
     "cra5_time_accumulate_f32": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cra5_time_finish_f32": (c_int, [c_size_t, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
+    "cra5_residual_spans": (c_size_t, [c_int, c_int, c_int]),
+    "cra5_residual_count_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cra5_residual_scan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cra5_residual_emit_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cra5_residual_apply_f32": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_void_p,
+                                                                                            c_size_t, c_void_p, c_void_p,
+                                                                                            c_size_t, c_void_p]),
+    "cra5_residual_gather_f32": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] + [c_int] * 6 + [c_void_p, c_size_t, c_void_p,
+                                                                                             c_void_p]),
     "cra5_transpose_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "cra5_pixel_shuffle_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "cra5_conv_im2col_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 12 + [c_void_p]),

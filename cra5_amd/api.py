@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import binfmt, ops, subset
+from . import residual as _res
 from .config import RuntimeConfig, runtime_setting
 from .zoo import vaeformer_pretrained
 
@@ -279,9 +280,19 @@ class cra5_api:
         with torch.no_grad():
             return self.net.compress_from_latent(y)
 
-    def encode_era5_as_bin(self, time_stamp, save_root=None, return_format='bin', data=None):
-        """cra5_api.py:81-125."""
+    def encode_era5_as_bin(self, time_stamp, save_root=None, return_format='bin', data=None, max_error=None,
+                           max_fraction=0.25):
+        """cra5_api.py:81-125.  max_error (a positive number: that bound in normalised units on every channel | a dict
+        {variable: bound in physical units}; residual.resolve_tolerance): the frame's own decode is corrected against the
+        staged truth on the GPU and the corrections are written beside the unchanged .bin as {save_root}/{yyyy}/{ts}.res -
+        decode with residual=True and every point of the corrected channels is within its bound (DESIGN.md section 4,
+        "Residual layer").  The dict gains residual = dict(path, bytes, records, escapes, per_channel, tol); more
+        corrections than max_fraction of the corrected channels' points raise ResidualBudgetError, no .res is written."""
         save_root = save_root or self.local_root
+        tol = self._residual_tol(max_error)
+        if tol is not None and return_format in ('latent', 'quantized'):
+            raise ValueError(f"encode_era5_as_bin: max_error writes a sidecar beside the .bin; return_format={return_format!r} "
+                             "writes none")
         st1 = time.time()
         frame = self._frame(time_stamp, data)
         st2 = time.time()
@@ -305,15 +316,21 @@ class cra5_api:
                 s = self.net._latent_side_guarded(y)
                 return s["y_hat"].reshape(y.shape).unsqueeze(0)
             output = {"strings": [[y_str], [z_str]], "z_shape": torch.Size([self.net.Hz, self.net.Wz])}
+            year = time_stamp.split('-')[0]
+            file_url = f'{save_root}/{year}/{time_stamp}.bin'
+            side = None
+            if tol is not None:
+                side = self._residual_encode(time_stamp, frame, y_str, z_str, output["z_shape"], tol, max_fraction)
         st3 = time.time()
-        year = time_stamp.split('-')[0]
-        file_url = f'{save_root}/{year}/{time_stamp}.bin'
         os.makedirs(os.path.dirname(file_url), exist_ok=True)
         with Path(file_url).open("wb") as f:
             binfmt.write_bin(f, output["strings"], output["z_shape"])
+        res = dict(output=output, save_path=file_url)
+        if side is not None:
+            res["residual"] = self._residual_write(side, file_url)
         st4 = time.time()
-        return dict(output=output, reading_time=st2 - st1, encoding_time=st3 - st2, saving_time=st4 - st3,
-                    save_path=file_url)
+        res.update(reading_time=st2 - st1, encoding_time=st3 - st2, saving_time=st4 - st3)
+        return res
 
     # ------------------------------------------------------------------ visualisation (cra5_api.py:273-341)
     @staticmethod
@@ -446,9 +463,19 @@ class cra5_api:
                     self.phase_log.append((threading.get_ident(), direction, t1, time.perf_counter()))
         return turn()
 
-    def _encode_one(self, ts, arr, save_root, write=True):
-        """One frame of the batch encode on the calling frame thread (its stream, its pinned / device buffers)."""
-        return self._encode_staged(ts, arr, save_root, write)[0]
+    def _encode_one(self, ts, arr, save_root, write=True, tol=None, max_fraction=None):
+        """One frame of the batch encode on the calling frame thread (its stream, its pinned / device buffers).  tol
+        (float32 [C], _residual_tol): the thread then decodes its own strings and writes the residual sidecar."""
+        enc, x = self._encode_staged(ts, arr, save_root, write)
+        if tol is not None:
+            out = enc["output"]
+            t0 = time.time()
+            with torch.no_grad():
+                side = self._residual_encode(ts, x, out["strings"][0][0], out["strings"][1][0], out["z_shape"], tol,
+                                             max_fraction)
+            enc["residual"] = self._residual_write(side, enc["save_path"], write)
+            enc["encoding_time"] += time.time() - t0
+        return enc
 
     def _encode_staged(self, ts, arr, save_root, write=True):
         """_encode_one -> (its dict, the frame on the device: this thread's staged copy, which the compress path only
@@ -481,20 +508,27 @@ class cra5_api:
         return dict(output=output, reading_time=t1 - t0, encoding_time=t2 - t1, saving_time=time.time() - t2,
                     save_path=file_url), x
 
-    def encode_era5_batch(self, time_stamps, data=None, save_root=None, workers=12, write=True):
+    def encode_era5_batch(self, time_stamps, data=None, save_root=None, workers=12, write=True, max_error=None,
+                          max_fraction=0.25):
         """encode_era5_as_bin for many time stamps (`data`: matching list of host arrays, or None to read
-        the NetCDF files).  Returns the list of per-frame dicts (same keys as encode_era5_as_bin)."""
+        the NetCDF files).  Returns the list of per-frame dicts (same keys as encode_era5_as_bin).
+        max_error / max_fraction (encode_era5_as_bin): after the compress phase every frame thread decodes its own
+        strings, quantises the residual against the staged truth on the GPU and writes {ts}.res beside the (byte-identical)
+        {ts}.bin; a frame over the budget ends the call with ResidualBudgetError."""
         save_root = save_root or self.local_root
         self.net._require_gpu()
+        tol = self._residual_tol(max_error)
         frames = list(data) if data is not None else [None] * len(time_stamps)
-        return self._pipeline(workers).map(lambda it: self._encode_one(it[0], it[1], save_root, write),
+        return self._pipeline(workers).map(lambda it: self._encode_one(it[0], it[1], save_root, write, tol, max_fraction),
                                            list(zip(time_stamps, frames)))
 
-    def _decode_one(self, i, path, denorm, out=None, sink=None, channels=None, box=None, step=None, coarsen=None):
+    def _decode_one(self, i, path, denorm, out=None, sink=None, channels=None, box=None, step=None, coarsen=None,
+                    res_path=None):
         """One frame of the batch decode on the calling frame thread: .bin -> x_hat (or its subset: canonical channels /
         box / step / coarsen of VAEformer._subset_args / _step_arg / _coarsen_arg) -> this thread's pinned buffer -> `sink` / `out[i]` / a fresh
         array."""
         lstrings, shape = self._read_bin(path)
+        side = self._residual_load(res_path) if res_path is not None else None
         with torch.no_grad():
             t_d = time.perf_counter()
             x_hat = self.net._decompress_frame(lstrings[0][0], lstrings[1][0], shape, True,
@@ -502,6 +536,8 @@ class cra5_api:
                                                std=self._std_flat if denorm else None, channels=channels, box=box,
                                                step=step, coarsen=coarsen)
             self._log("decompress", t_d)
+            if side is not None:
+                self._residual_correct(x_hat, side, channels, box, step, res_path)
             C, H, W = x_hat.shape[-3:]
             pin = self.net._pinned("api_x_out", (C, H, W), torch.float32)
             if sink is None and out is not None and self.batch_copy_threads > 1:
@@ -558,7 +594,7 @@ class cra5_api:
         return self._pipeline(workers).map(one, [(i, ts, a) for i, (ts, a) in enumerate(zip(time_stamps, frames))])
 
     def decode_batch(self, time_stamps=None, paths=None, return_format='de_normalized', out=None, workers=12, sink=None,
-                     variables=None, region=None, stride=None, coarsen=None):
+                     variables=None, region=None, stride=None, coarsen=None, residual=None):
         """decode_from_bin for many frames.  Returns a list of HOST float32 arrays [C, H, W] (views of `out`
         [n, C, H, W] when given, fresh arrays otherwise); the D2H of each reconstruction goes through the
         decoding thread's pinned buffer and overlaps the other frames' work.  `sink(i, frame)`: called on the decoding
@@ -570,7 +606,9 @@ class cra5_api:
         stride Hb / Wb count the kept rows / columns: stride=6 over the globe is [C', 121, 240]).
         coarsen (decode_from_bin): the same shapes as stride=coarsen, every point the area-weighted mean of its coarse
         cell - 1 / (k_lat * k_lon) of the bytes cross the host link; grid_box(region, coarsen=coarsen) gives lat / lon
-        and the cells' lat_bnds / lon_bnds."""
+        and the cells' lat_bnds / lon_bnds.
+        residual (decode_from_bin): True - the .res beside every .bin -, or one sidecar path per frame; every frame is
+        corrected on the device before it crosses the host link."""
         if paths is None:
             paths = [f'{self.local_root}/CRA5/{ts[:4]}/{ts}.bin' for ts in time_stamps]
         if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
@@ -578,15 +616,17 @@ class cra5_api:
         denorm = return_format != 'normalized'
         self.net._require_gpu()
         channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
+        sides = self._residual_arg("decode_batch", residual, list(paths), return_format, sel["coarsen"])
         shape = None
         if meta is not None:
             shape = (len(meta["variables"]), len(meta["lat"]), len(meta["lon"]))
         self._check_out(out, len(paths), shape)
 
-        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box, **sel),
+        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box,
+                                                                       res_path=sides[it[0]], **sel),
                                            list(enumerate(paths)))
 
-    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, coarsen=None, spectrum=False):
+    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, coarsen=None, spectrum=False, tol=None):
         """One frame of evaluate_batch on the calling frame thread: the truth is staged once into this thread's device
         frame buffer; the reconstruction comes from the in-memory strings (bin_path None) or from `bin_path`, and only
         the per-channel statistics leave the device.  coarsen = (k_lat, k_lon): both frames are coarsened on the device
@@ -611,6 +651,16 @@ class cra5_api:
             x_hat = self.net._decompress_frame(strings[0][0], strings[1][0], shape, True,
                                                mean=self._mean_flat, std=self._std_flat, coarsen=coarsen)
             self._log("decompress", t_d)
+            side = None
+            if tol is not None:
+                # the reconstruction a decode with the sidecar would see: quantise against the staged truth, correct in place
+                t_r = time.perf_counter()
+                side = self._residual_build(ts, x, x_hat, tol, None)
+                grid = tuple(x_hat.shape[-3:])
+                ops.residual_apply(x_hat.reshape(grid), side["records"], side["step"], grid)
+                if bin_path is None and save_root is not None:
+                    self._residual_write(side, enc["save_path"])
+                self._log("residual", t_r)
             t_m = time.perf_counter()
             C, H, W = x.shape[-3:]
             x = x.reshape(C, H, W)
@@ -639,10 +689,13 @@ class cra5_api:
                                              "resolved_wavenumber")})
         rep["bin_bytes"] = n_bytes
         rep["compression_ratio"] = C * H * W * 4 / n_bytes
+        if side is not None:
+            rep.update(res_bytes=len(side["blob"]), records=side["records_n"], escapes=side["escapes_n"], tol=side["tol"],
+                       compression_ratio_total=C * H * W * 4 / (n_bytes + len(side["blob"])))
         return rep
 
     def evaluate_batch(self, time_stamps, data=None, bins=None, save_root=None, workers=12, lat_weights="era5",
-                       coarsen=None, spectrum=False):
+                       coarsen=None, spectrum=False, max_error=None):
         """Per-variable reconstruction error of many frames, through the frame pipeline, without copying any
         reconstruction to the host.  Truth frames: `data` (a matching list of host arrays / tensors, physical units) or
         the NetCDF files of `time_stamps`.
@@ -661,10 +714,19 @@ class cra5_api:
         spectrum=True: every report also carries the zonal power spectra of metrics.zonal_spectrum on the same device
         pair (with coarsen=, the coarse pair): wavenumber int64 [K], power_truth / power_recon / power_error float64
         [C, K] and resolved_wavenumber int64 [C]; only the spectra leave the device.  The compared width (W, or the coarse
-        Wo) must have no prime factor above 5."""
+        Wo) must have no prime factor above 5.
+        max_error (encode_era5_as_bin; not with coarsen=): the tuning tool of the residual layer - the reconstruction is
+        corrected on the device before the metric and the spectrum, as a decode with the sidecar would see it, and every
+        report gains res_bytes (the sidecar's size), records, escapes, tol and compression_ratio_total = C * H * W * 4 /
+        (bin_bytes + res_bytes); compression_ratio stays that of the .bin.  No budget applies here.  With save_root (and
+        bins=None) the .res is written beside the .bin."""
         self.net._require_gpu()
         H, W = self.net.cfg['img_size']
         k = self.net._coarsen_arg(coarsen, None)
+        tol = self._residual_tol(max_error)
+        if tol is not None and k is not None:
+            raise ValueError("evaluate_batch: max_error with coarsen= is not supported - the correction belongs before the "
+                             "averaging, on the full grid; evaluate the two separately")
         extra = {}
         if k is not None:
             g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W, coarsen=k)
@@ -680,16 +742,17 @@ class cra5_api:
             raise ValueError("evaluate_batch: time_stamps, data and bins must have the same length")
         paths = list(bins) if bins is not None else [None] * n
         reps = self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights, k,
-                                                                         bool(spectrum)),
+                                                                         bool(spectrum), tol),
                                            list(zip(time_stamps, frames, paths)))
         for r in reps:
             r.update(extra)
         return reps
 
-    def _aggregate_one(self, path, denorm, channels, box, sel, frame_shape, acc, seq):
+    def _aggregate_one(self, path, denorm, channels, box, sel, frame_shape, acc, seq, res_path=None):
         """One frame of aggregate_batch on the calling frame thread: .bin -> x_hat (or its subset) -> folded into the
         group's device accumulators as turn `seq`, on this frame's stream.  Nothing crosses to the host."""
         lstrings, shape = self._read_bin(path)
+        side = self._residual_load(res_path) if res_path is not None else None
         with torch.no_grad():
             t_d = time.perf_counter()
             x_hat = self.net._decompress_frame(lstrings[0][0], lstrings[1][0], shape, True,
@@ -697,6 +760,8 @@ class cra5_api:
                                                std=self._std_flat if denorm else None, channels=channels, box=box,
                                                **sel)
             self._log("decompress", t_d)
+            if side is not None:
+                self._residual_correct(x_hat, side, channels, box, sel["step"], res_path)
             t_a = time.perf_counter()
             if tuple(x_hat.shape[-3:]) != frame_shape or x_hat.numel() != frame_shape[0] * frame_shape[1] * frame_shape[2]:
                 raise ValueError(f"{path}: the reconstruction is {tuple(x_hat.shape)}, the accumulators {frame_shape}")
@@ -705,7 +770,7 @@ class cra5_api:
 
     def aggregate_batch(self, time_stamps=None, paths=None, stats=("mean", "std", "min", "max"), groups=None, ddof=0,
                         variables=None, region=None, stride=None, return_format='de_normalized', workers=12, to_host=True,
-                        coarsen=None):
+                        coarsen=None, residual=None):
         """Per-grid-point statistics over time of many decoded frames (a daily or monthly mean, the spread, the extremes),
         reduced on the GPU: every .bin is decoded through the frame pipeline exactly as decode_batch decodes it, and
         instead of crossing the host link the reconstruction is folded into device accumulators (cra5_amd.timestats,
@@ -719,6 +784,8 @@ class cra5_api:
           variables / region / stride / coarsen / return_format ('de_normalized' | 'normalized'): as in decode_batch -
             with coarsen=k the statistics are those of the area-averaged frames, in 1 / (k_lat * k_lon) of the accumulator
             memory and of the final host copy.
+          residual (decode_from_bin): True or one sidecar path per frame - every frame is corrected on the device before
+            it is folded in: the statistics are those of the error-bounded frames.
         Returns a dict: variables, lat, lon (also for the full grid; with coarsen also coarsen, lat_bnds, lon_bnds), n (int; with groups an int64 [G] array), groups
         (the labels, when given) and per statistic a HOST float32 array [C', Hb, Wb] ([G, C', Hb, Wb] with groups), or
         with to_host=False a device tensor of that shape.  A frame that fails (a missing file, a StreamDesyncError) ends
@@ -753,6 +820,7 @@ class cra5_api:
             raise ValueError(f"aggregate_batch: std with ddof = {ddof} needs more than {ddof} frame(s) per group; "
                              + (f"group {labels[g]!r} holds {counts[g]}" if groups is not None else f"{counts[g]} given"))
         channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
+        sides = self._residual_arg("aggregate_batch", residual, paths, return_format, sel["coarsen"])
         if meta is None:
             H, W = self.net.cfg['img_size']
             g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W)
@@ -770,7 +838,7 @@ class cra5_api:
 
         def one(i):
             try:
-                self._aggregate_one(paths[i], denorm, channels, box, sel, frame_shape, accs[member[i]], seqs[i])
+                self._aggregate_one(paths[i], denorm, channels, box, sel, frame_shape, accs[member[i]], seqs[i], sides[i])
             except BaseException as e:
                 for a in accs:       # nobody waits for this frame's turn, and the call ends with this frame's error
                     a.abort(e)
@@ -798,6 +866,133 @@ class cra5_api:
         self._log("d2h", t0)
         return res
 
+    # ------------------------------------------------------------------ residual layer (cra5_amd/residual.py)
+    def _residual_tol(self, max_error):
+        """max_error -> the per-channel tolerance, float32 numpy [C] in physical units (residual.resolve_tolerance), or
+        None."""
+        if max_error is None:
+            return None
+        return _res.resolve_tolerance(max_error, self.vname_to_channels, self._std_flat.detach().cpu().numpy())
+
+    def _residual_build(self, ts, x, x_hat, tol, max_fraction):
+        """Quantise the truth x against the plain de-normalised decode x_hat (both whole frames on the device) -> dict(blob:
+        the sidecar's bytes, records: the four device arrays, step: device fp32 [C], records_n, escapes_n, per_channel, tol).
+        The witnesses are read from x_hat here, before anything corrects it; the arrays reach the host through this
+        thread's pinned buffer.  ResidualBudgetError before anything is copied."""
+        C, H, W = (int(v) for v in x_hat.shape[-3:])
+        if x.numel() != C * H * W or tuple(x.shape[-3:]) != (C, H, W):
+            raise ValueError(f"{ts}: the truth frame is {tuple(x.shape)}, the reconstruction {(C, H, W)}")
+        x, x_hat = x.reshape(C, H, W), x_hat.reshape(C, H, W)
+        dev = x_hat.device
+        widx = _res.witness_indices(C, H, W)
+        got = ops.residual_gather(x_hat, torch.from_numpy(widx.view(np.int32)).to(dev), (C, H, W))
+        idx, q, eidx, ebits, per = ops.residual_quantize(x, x_hat, tol)
+        names = [self.channels_to_vname.get(c, str(c)) for c in range(C)]
+        _res.check_budget(per, tol, H * W, max_fraction, names)
+        parts, off = [], 0
+        for t in (got.reshape(-1), idx, q, eidx, ebits):
+            parts.append((off, t))
+            off = (off + t.numel() * t.element_size() + 15) // 16 * 16
+        cap = 1 << max(16, (off - 1).bit_length())        # grows in powers of two: few re-allocations of pinned memory
+        pin = self.net._pinned("api_res_out", (cap,), torch.uint8)
+        host = []
+        with self._link("d2h"):
+            for o, t in parts:
+                h = pin[o:o + t.numel() * t.element_size()].view(t.dtype)
+                h.copy_(t, non_blocking=True)
+                host.append(h.numpy())
+            torch.cuda.current_stream().synchronize()
+        wbits = host[0].reshape(-1, 2)[:, 1].view(np.uint32)
+        blob = _res.pack(C, H, W, tol, widx, wbits, host[1].view(np.uint32), host[2], host[3].view(np.uint32),
+                         host[4].view(np.uint32))
+        return dict(blob=blob, records=(idx, q, eidx, ebits), step=torch.from_numpy(np.float32(2) * tol).to(dev),
+                    records_n=int(per[:, 0].sum()), escapes_n=int(per[:, 1].sum()), per_channel=per, tol=tol)
+
+    def _residual_encode(self, ts, x, y_str, z_str, shape, tol, max_fraction):
+        """The encoder's side of the residual layer for one frame: decode the frame's own strings (the whole frame,
+        de-normalised: the x_hat every decoder of this .bin computes, bit for bit) and quantise the staged truth against
+        it."""
+        t_r = time.perf_counter()
+        x_hat = self.net._decompress_frame(y_str, z_str, shape, True, mean=self._mean_flat, std=self._std_flat)
+        side = self._residual_build(ts, x, x_hat, tol, max_fraction)
+        self._log("residual", t_r)
+        return side
+
+    @staticmethod
+    def _residual_write(side, bin_path, write=True):
+        """Write the sidecar beside `bin_path` -> the `residual` entry of the encode dict."""
+        path = _res.sidecar_path(bin_path)
+        if write:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with Path(path).open("wb") as f:
+                f.write(side["blob"])
+        return dict(path=path, bytes=len(side["blob"]), records=side["records_n"], escapes=side["escapes_n"],
+                    per_channel=side["per_channel"], tol=side["tol"])
+
+    @staticmethod
+    def _residual_arg(what, residual, bin_paths, return_format, coarsen):
+        """residual= of the decode methods -> one sidecar path (or None) per frame.  True: the .res beside each .bin."""
+        if residual is None or residual is False:
+            return [None] * len(bin_paths)
+        if return_format not in ('de_normalized', 'de_normlized'):
+            raise ValueError(f"{what}: residual= corrects the de-normalised reconstruction (the tolerances are in physical "
+                             f"units); return_format={return_format!r} is not supported with it")
+        if coarsen is not None:
+            raise ValueError(f"{what}: residual= with coarsen= is not supported - the correction belongs before the "
+                             "averaging, on points the coarsened decode never materialises")
+        if residual is True:
+            sides = [_res.sidecar_path(p) for p in bin_paths]
+        elif isinstance(residual, (str, bytes, os.PathLike)):
+            if len(bin_paths) != 1:
+                raise ValueError(f"{what}: residual= takes True or one sidecar path per frame, got one path for "
+                                 f"{len(bin_paths)} frames")
+            sides = [residual]
+        else:
+            sides = list(residual)
+            if len(sides) != len(bin_paths) or not all(isinstance(p, (str, bytes, os.PathLike)) for p in sides):
+                raise ValueError(f"{what}: residual= takes True or one sidecar path per frame ({len(bin_paths)} frames)")
+        for p in sides:
+            if not os.path.exists(p):
+                raise FileNotFoundError(f"{what}: residual sidecar {p} not found (written by encode_era5_as_bin / "
+                                        "encode_era5_batch with max_error=)")
+        return sides
+
+    def _residual_load(self, path):
+        """Read and check a sidecar (residual.unpack) -> dict with its records, step, witness indexes on the device."""
+        with open(path, "rb") as f:
+            side = _res.unpack(f.read())
+        grid = (self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size'])
+        if (side["C"], side["H"], side["W"]) != grid:
+            raise ValueError(f"{path}: the sidecar belongs to a frame of {(side['C'], side['H'], side['W'])}, the model's "
+                             f"grid is {grid}")
+        dev = self.net.device
+
+        def up(a):
+            return torch.from_numpy(a.view(np.int16 if a.dtype.itemsize == 2 else np.int32)).to(dev, non_blocking=True)
+        side["records"] = (up(side["idx"]), up(side["q"]), up(side["eidx"]), up(side["ebits"]))
+        side["widx_dev"] = up(side["widx"])
+        side["step"] = torch.from_numpy(np.float32(2) * side["tol"]).to(dev, non_blocking=True)
+        side["grid"] = grid
+        return side
+
+    def _residual_correct(self, x_hat, side, channels, box, step, what):
+        """Correct the decode's device output IN PLACE (x_hat [.., C', Ho, Wo]: canonical channels / box / step of
+        _subset_args / _step_arg).  The sidecar's witnesses inside the subset are compared with the plain decode first:
+        ResidualMismatchError before anything is written."""
+        out = x_hat.reshape(x_hat.shape[-3:])
+        if out.data_ptr() != x_hat.data_ptr():
+            raise RuntimeError("residual: the decode's output is not contiguous")
+        lut = None
+        if channels is not None:
+            lut = np.full(side["C"], -1, dtype=np.int32)
+            lut[list(channels)] = np.arange(len(channels), dtype=np.int32)
+            lut = torch.from_numpy(lut).to(out.device)
+        t_r = time.perf_counter()
+        got = ops.residual_gather(out, side["widx_dev"], side["grid"], lut, box, step).cpu().numpy()
+        _res.check_witnesses(got[:, 0] != 0, got[:, 1].view(np.uint32), side["wbits"], str(what))
+        ops.residual_apply(out, side["records"], side["step"], side["grid"], lut, box, step)
+        self._log("residual", t_r)
+
     # ------------------------------------------------------------------ decode
     def _read_bin(self, bin_path):
         with Path(bin_path).open("rb") as f:
@@ -821,7 +1016,7 @@ class cra5_api:
             return self.net.decode_latent(y_hat, channels=channels, box=box, **sel)
 
     def decode_from_bin(self, time_stamp=None, custom_path=None, return_format='de_normalized', to_host=False, out=None,
-                        variables=None, region=None, stride=None, coarsen=None):
+                        variables=None, region=None, stride=None, coarsen=None, residual=None):
         """cra5_api.py:153-192.  `to_host=True` (or `out=` a float32 array of the frame's shape): `x_hat` comes back
         as a HOST numpy array through the pinned staging buffer instead of a device tensor.
         variables: names of channel_vname_mapping() (e.g. ["z_500", "t_850", "t2m"]), output channels in that order;
@@ -839,7 +1034,14 @@ class cra5_api:
         conservative remapping): decode_from_bin(ts, coarsen=6) is the conservative 1.5 deg field
         [C', 121, 240].  Computed on the GPU in fixed float64 arithmetic: bit-identical from run to run, a region's result
         the sub-block of the globe's; NaN / inf in a window propagate.  The dict also carries `coarsen`, `lat_bnds`
-        [Hb, 2] (north, south) and `lon_bnds` [Wb, 2] (west, east)."""
+        [Hb, 2] (north, south) and `lon_bnds` [Wb, 2] (west, east).
+        residual: None | True (the .res beside the .bin: the same path with the extension replaced; a missing file is an
+        error) | a sidecar path, written by encode_era5_as_bin(max_error=...).  Its corrections are added on the GPU, in
+        place on the decode's output before it goes anywhere else: every point of the corrected channels is then the truth
+        bit for bit or within the sidecar's tolerance of it, and a variables / region / stride subset is the slice of the
+        corrected full frame, bit for bit.  The sidecar's witness points that fall inside the decoded subset are compared
+        with the plain decode first (those outside it are not checked): a difference raises ResidualMismatchError and
+        nothing is corrected.  Only with return_format 'de_normalized' and without coarsen= (ValueError otherwise)."""
         if return_format == 'latent' and (variables is not None or region is not None or stride is not None
                                           or coarsen is not None):
             raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region / stride / "
@@ -848,8 +1050,11 @@ class cra5_api:
             raise ValueError(f"unknown return_format {return_format!r}")
         channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
         bin_path = custom_path or f'{self.local_root}/CRA5/{time_stamp[:4]}/{time_stamp}.bin'
+        res_path = self._residual_arg("decode_from_bin", residual if residual is None or isinstance(residual, bool) else [residual],
+                                      [bin_path], return_format, sel["coarsen"])[0]
         decoding_start = time.time()
         lstrings, shape = self._read_bin(bin_path)
+        side = self._residual_load(res_path) if res_path is not None else None
         with torch.no_grad():
             y_hat = self.net.decompress(lstrings, shape, return_format='latent')
             if return_format == 'latent':
@@ -860,6 +1065,8 @@ class cra5_api:
                 # fused de-normalisation in the overlap-add store
                 x_hat = self.net._decode_guarded(y_hat[0], mean=self._mean_flat, std=self._std_flat, channels=channels,
                                                  box=box, **sel)
+                if side is not None:
+                    self._residual_correct(x_hat, side, channels, box, sel["step"], res_path)
             if to_host or out is not None:
                 src = x_hat.reshape(x_hat.shape[-3:]).contiguous()
                 if out is None:

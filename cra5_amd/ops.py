@@ -829,6 +829,170 @@ def zonal_spectrum(x_hat, x, lat_w=None, out=None):
     return power, nonfinite
 
 
+RESIDUAL_SPAN = 4096     # CRA5_RESIDUAL_SPAN
+RESIDUAL_MAX_TOL = 1e30  # step = 2 * tol must stay finite in fp32
+
+
+def _residual_frame(what, name, t):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a torch tensor, got {type(t).__name__}")
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise TypeError(f"{what}: {name} must be a contiguous fp32 device tensor")
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"{what}: {name} must be [C, H, W], got {tuple(t.shape)}")
+
+
+def _residual_array(what, name, t, dtype, device, shape=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise TypeError(f"{what}: {name} must be a contiguous {dtype} device tensor")
+    if t.device != device:
+        raise ValueError(f"{what}: {name} is on {t.device}, the frame on {device}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must be {list(shape)}, got {list(t.shape)}")
+
+
+def residual_tolerance(tol, C, what="residual_quantize"):
+    """tol (array-like [C]) -> float32 numpy [C], checked: every entry finite > 0 and <= RESIDUAL_MAX_TOL, or +inf (the
+    channel is not corrected)."""
+    if isinstance(tol, torch.Tensor):
+        tol = tol.detach().cpu().numpy()
+    t = np.asarray(tol)
+    if t.dtype.kind != "f":
+        raise TypeError(f"{what}: tol must be a float array, got dtype {t.dtype}")
+    if t.shape != (C,):
+        raise ValueError(f"{what}: tol must be [{C}] (one tolerance per channel), got {list(t.shape)}")
+    t = np.ascontiguousarray(t, dtype=np.float32)
+    ok = (np.isposinf(t) | (np.isfinite(t) & (t > 0) & (t <= np.float32(RESIDUAL_MAX_TOL))))
+    if not ok.all():
+        c = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f"{what}: tol[{c}] = {t[c]!r}: a tolerance is finite in (0, {RESIDUAL_MAX_TOL:g}] or +inf "
+                         "(channel not corrected)")
+    return t
+
+
+def residual_quantize(x, x_hat, tol):
+    """cra5_residual_count_f32 / _scan / _emit_f32 (csrc/residual.hip): the corrections that bring the decode x_hat within
+    tol of the truth x.  x, x_hat: contiguous fp32 device tensors [C, H, W] of one shape on one device (C * H * W < 2^32);
+    tol: float [C] (numpy / list / tensor; residual_tolerance).  -> (idx, q, eidx, ebits, per_channel): device tensors
+    idx int32 [n] (the uint32 bit patterns of the flat global indexes), q int16 [n], eidx int32 [m], ebits int32 [m] (the
+    bits of x at the escapes), each ascending in idx, and per_channel, a HOST int64 array [C, 2] of (records, escapes).
+    On the current stream; the call waits for the counts (they size the arrays)."""
+    what = "residual_quantize"
+    _residual_frame(what, "x", x)
+    _residual_frame(what, "x_hat", x_hat)
+    if tuple(x.shape) != tuple(x_hat.shape) or x.device != x_hat.device:
+        raise ValueError(f"{what}: x {tuple(x.shape)} on {x.device} and x_hat {tuple(x_hat.shape)} on {x_hat.device} must "
+                         "have one shape on one device")
+    C, H, W = x.shape
+    spans = lib().cra5_residual_spans(C, H, W)
+    if spans == 0:
+        raise ValueError(f"{what}: x {(C, H, W)}: a frame needs C * H * W < 2^32 (the indexes are uint32)")
+    t = residual_tolerance(tol, C, what)
+    dev = x.device
+    tol_d = torch.from_numpy(t).to(dev)
+    counts = torch.empty((spans, 2), device=dev, dtype=torch.int32)
+    offs = torch.empty((spans + 1, 2), device=dev, dtype=torch.int32)
+    chan = torch.empty((C, 2), device=dev, dtype=torch.int64)
+    ev = TIMER.start() if TIMER else None
+    check(lib().cra5_residual_count_f32(_p(x), _p(x_hat), _p(tol_d), C, H, W, _p(counts), _stream()), "cra5_residual_count_f32")
+    if TIMER:
+        TIMER.stop("residual_count", ev, 8.0 * C * H * W)
+    check(lib().cra5_residual_scan(_p(counts), C, H, W, _p(offs), _p(chan), _stream()), "cra5_residual_scan")
+    per_channel = chan.cpu().numpy()
+    n, m = (int(v) for v in per_channel.sum(axis=0))
+    idx = torch.empty((n,), device=dev, dtype=torch.int32)
+    q = torch.empty((n,), device=dev, dtype=torch.int16)
+    eidx = torch.empty((m,), device=dev, dtype=torch.int32)
+    ebits = torch.empty((m,), device=dev, dtype=torch.int32)
+    ev = TIMER.start() if TIMER else None
+    check(lib().cra5_residual_emit_f32(_p(x), _p(x_hat), _p(tol_d), C, H, W, _p(offs), _p(idx) if n else None,
+                                       _p(q) if n else None, n, _p(eidx) if m else None, _p(ebits) if m else None, m,
+                                       _stream()), "cra5_residual_emit_f32")
+    if TIMER:
+        TIMER.stop("residual_emit", ev, 8.0 * C * H * W)
+    return idx, q, eidx, ebits, per_channel
+
+
+def _residual_geometry(what, out, grid, chan_lut, box, stride):
+    """-> the 13 geometry arguments of cra5_residual_apply_f32 / _gather_f32 after `out`, checked."""
+    _residual_frame(what, "out", out)
+    try:
+        C, H, W = (int(v) for v in grid)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: grid must be (C, H, W) of the global frame, got {grid!r}") from None
+    if lib().cra5_residual_spans(C, H, W) == 0:
+        raise ValueError(f"{what}: grid {(C, H, W)}: a frame needs C * H * W < 2^32")
+    Cs, Ho, Wo = out.shape
+    if chan_lut is not None:
+        _residual_array(what, "chan_lut", chan_lut, torch.int32, out.device, (C,))
+    elif Cs != C:
+        raise ValueError(f"{what}: out has {Cs} channels, the grid {C}: pass chan_lut")
+    r0, r1, c0, nc = (0, H, 0, W) if box is None else (int(v) for v in box)
+    sy, sx = (1, 1) if stride is None else (int(v) for v in stride)
+    if not (0 <= r0 < r1 <= H and 0 <= c0 < W and 1 <= nc <= W):
+        raise ValueError(f"{what}: box {box!r}: need 0 <= r0 < r1 <= {H}, 0 <= c0 < {W}, 1 <= nc <= {W}")
+    if sy < 1 or sx < 1 or W % sx:
+        raise ValueError(f"{what}: stride {stride!r}: need s_lat >= 1, s_lon >= 1 and {W} % s_lon == 0")
+    from .subset import kept_points
+    rows, cols = kept_points((r0, r1, c0, nc), (sy, sx), W)
+    if (Ho, Wo) != (len(rows), len(cols)):
+        raise ValueError(f"{what}: out is [{Cs}, {Ho}, {Wo}], the box / stride keep {len(rows)} rows and {len(cols)} columns")
+    return (Cs, Ho, Wo, C, H, W, _p(chan_lut), r0, r1, sy, c0, nc, sx), C
+
+
+def _residual_records(what, records, device):
+    try:
+        idx, q, eidx, ebits = records
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: records must be (idx, q, eidx, ebits)") from None
+    for name, t, dt in (("idx", idx, torch.int32), ("q", q, torch.int16), ("eidx", eidx, torch.int32),
+                        ("ebits", ebits, torch.int32)):
+        _residual_array(what, f"records.{name}", t, dt, device)
+        if t.dim() != 1:
+            raise ValueError(f"{what}: records.{name} must be one-dimensional, got {list(t.shape)}")
+    if idx.numel() != q.numel() or eidx.numel() != ebits.numel():
+        raise ValueError(f"{what}: records: idx / q hold {idx.numel()} / {q.numel()} entries, eidx / ebits {eidx.numel()} / "
+                         f"{ebits.numel()}")
+    return idx, q, eidx, ebits
+
+
+def residual_apply(out, records, step, grid, chan_lut=None, box=None, stride=None):
+    """cra5_residual_apply_f32: correct the decode's output `out` (contiguous fp32 device tensor [C', Ho, Wo]) IN PLACE.
+    records = (idx, q, eidx, ebits) of residual_quantize (global indexes of the frame grid = (C, H, W)); step: contiguous
+    fp32 device tensor [C] (2 * tol); chan_lut: int32 device tensor [C], the output channel of every global channel or -1
+    (None: out holds every channel in order); box (r0, r1, c0, nc) and stride (s_lat, s_lon) as in subset.kept_points
+    (None: the globe / every point).  A record adds fl32(q * step[c]) to its point, an escape stores the truth's bits;
+    entries outside `out` are skipped.  On the current stream."""
+    what = "residual_apply"
+    geom, C = _residual_geometry(what, out, grid, chan_lut, box, stride)
+    idx, q, eidx, ebits = _residual_records(what, records, out.device)
+    _residual_array(what, "step", step, torch.float32, out.device, (C,))
+    n, m = idx.numel(), eidx.numel()
+    ev = TIMER.start() if TIMER else None
+    check(lib().cra5_residual_apply_f32(_p(out), *geom, _p(step), _p(idx) if n else None, _p(q) if n else None, n,
+                                        _p(eidx) if m else None, _p(ebits) if m else None, m, _stream()),
+          "cra5_residual_apply_f32")
+    if TIMER:
+        TIMER.stop("residual_apply", ev, 14.0 * n + 16.0 * m)
+    return out
+
+
+def residual_gather(out, widx, grid, chan_lut=None, box=None, stride=None):
+    """cra5_residual_gather_f32: the bits of `out` (geometry as in residual_apply) at the global indexes widx (int32
+    device tensor [nw], uint32 bit patterns) -> int32 device tensor [nw, 2]: (1, bits) or (0, 0) for a point outside
+    `out`.  On the current stream."""
+    what = "residual_gather"
+    geom, _ = _residual_geometry(what, out, grid, chan_lut, box, stride)
+    _residual_array(what, "widx", widx, torch.int32, out.device)
+    if widx.dim() != 1:
+        raise ValueError(f"{what}: widx must be one-dimensional, got {list(widx.shape)}")
+    nw = widx.numel()
+    got = torch.empty((nw, 2), device=out.device, dtype=torch.int32)
+    check(lib().cra5_residual_gather_f32(_p(out), *geom, _p(widx) if nw else None, nw, _p(got) if nw else None, _stream()),
+          "cra5_residual_gather_f32")
+    return got
+
+
 TIME_ACCUMULATORS = (("sum", torch.float64), ("sumsq", torch.float64), ("min", torch.float32), ("max", torch.float32))
 
 

@@ -387,6 +387,40 @@ int cra5_time_accumulate_f32(const float *x, size_t n, int first, double *sum, d
 int cra5_time_finish_f32(size_t n, long long count, int ddof, const double *sum, const double *sumsq, float *mean,
                          float *stdv, void *stream);
 
+/* Error-bounded residual layer (csrc/residual.hip; DESIGN.md section 4, "Residual layer").  x (truth), x_hat (the plain
+ * decode) [C][H][W] fp32, tol [C] fp32 on the device: finite > 0, or +inf = the channel is not corrected.  Per point of a
+ * corrected channel, step = fp32 2 * tol:  d = (double)x - (double)x_hat,  q = rint(d / (double)step);  d not finite or
+ * |q| > 32767: an ESCAPE;  t = x_hat for q == 0, else fl32(x_hat + fl32((float)q * step)) (two roundings, no FMA);
+ * |(double)x - (double)t| <= (double)tol: accepted - q != 0 stores the RECORD (idx, q), q == 0 nothing -, else an ESCAPE
+ * (idx, the 32 bits of x).  idx = (c * H + r) * W + col as uint32: C * H * W < 2^32 (and H * W < 2^31).
+ * Quantise = three calls on one stream, no atomics, the arrays identical from run to run and ascending in idx:
+ *   count: counts [S][2] uint32 = (records, escapes) of every span of CRA5_RESIDUAL_SPAN elements (spans never straddle a
+ *     channel; S = cra5_residual_spans = C * ceil(H * W / span), 0 for unsupported dimensions);
+ *   scan:  offs [S + 1][2] uint32 = exclusive prefix sums of counts (last row: the totals n, m), chan [C][2] int64 = the
+ *     totals per channel (one block);
+ *   emit:  idx [n] uint32, q [n] int16, eidx [m] uint32, ebits [m] uint32 at the scanned offsets (n, m: the capacities, the
+ *     totals of the scan; nothing is stored past them; n == m == 0 launches nothing and the four pointers may be NULL).
+ * Frames: any 4-byte aligned base; a span whose two start addresses are 16-byte aligned is read with 16-byte loads.
+ * Apply: out [Cs][Ho][Wo] fp32, the decode's output for chan_lut [C] int32 (output channel of c, -1 = absent; NULL = the
+ * identity), the rows r of [r0, r1) with r % s_lat == 0 and the columns col with (col - c0) mod W < nc and col % s_lon == 0
+ * (W % s_lon == 0), in that order - Ho / Wo must be their counts.  One thread per entry: a record adds fl32((float)q *
+ * step[c]) to its point (step [C] fp32), an escape stores its bits; entries outside the output are skipped.  gather: got
+ * [nw][2] uint32 = (1, the bits of out at widx[i]) or (0, 0) for a point outside the output - the witness check, run before
+ * the apply.  CRA5_ERR_ARG, before any device work, for bad dimensions / geometry, NULL or misaligned pointers. */
+#define CRA5_RESIDUAL_SPAN 4096
+size_t cra5_residual_spans(int C, int H, int W);
+int cra5_residual_count_f32(const float *x, const float *x_hat, const float *tol, int C, int H, int W, uint32_t *counts,
+                            void *stream);
+int cra5_residual_scan(const uint32_t *counts, int C, int H, int W, uint32_t *offs, long long *chan, void *stream);
+int cra5_residual_emit_f32(const float *x, const float *x_hat, const float *tol, int C, int H, int W, const uint32_t *offs,
+                           uint32_t *idx, int16_t *q, size_t n, uint32_t *eidx, uint32_t *ebits, size_t m, void *stream);
+int cra5_residual_apply_f32(float *out, int Cs, int Ho, int Wo, int C, int H, int W, const int *chan_lut, int r0, int r1,
+                            int s_lat, int c0, int nc, int s_lon, const float *step, const uint32_t *idx, const int16_t *q,
+                            size_t n, const uint32_t *eidx, const uint32_t *ebits, size_t m, void *stream);
+int cra5_residual_gather_f32(const float *out, int Cs, int Ho, int Wo, int C, int H, int W, const int *chan_lut, int r0,
+                             int r1, int s_lat, int c0, int nc, int s_lon, const uint32_t *widx, size_t nw, uint32_t *got,
+                             void *stream);
+
 /* out[c][r] = in[r][c] (token-major <-> NCHW plumbing, vit_nlc.py:484, 684). */
 int cra5_transpose_f32(const float *in, int ld_in, float *out, int ld_out, int rows, int cols,
                        void *stream);
