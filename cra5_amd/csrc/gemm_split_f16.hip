@@ -53,9 +53,14 @@ namespace {
 constexpr int BK = 32;         // elements per k-step
 
 // gelu(x) = x * Phi(x),  Phi(x) = 0.5 erfc(-x / sqrt 2),  erfc(t) = exp(-t^2) * k P(k), k = 1/(1 + 0.4 t)
-// for t >= 0 (degree-7 least-squares fit, |erfc error| <= 8.3e-9 on [0, 6]; evaluated in fp32 the
-// gelu error against fp64 is 1.1e-7 RMS / 6.1e-7 max over [-9, 9] - below torch's own fp32
-// erf-based gelu, 1.7e-7 / 1.3e-6; tests/test_kernels_gpu.py pins it).  One rcp + one exp2 + 10 FMAs,
+// for t >= 0 (degree-7 least-squares fit: in float64 |erfc error| <= 8.3e-9 for t >= 0.88 and up to 7.3e-8 below it, at
+// t = 0, where the coefficients sum to 1 - 7.3e-8; at most 4.5e-4 RELATIVE for x in [-6, -3], where an erf-based gelu
+// returns 0).  Evaluated on the MI355X the gelu error against float64 is 5.8e-8 RMS / 3.8e-7 max over one point every
+// 3.7e-4 of [-9, 9) - torch's fp32 CPU gelu: 1.4e-7 / 9.6e-7 on the same points.  Pinned per element, in every epilogue
+// that calls it, by tests/test_domain_gpu.py::test_gelu_generic_epilogue, ::test_gelu_straight_line_epilogue and
+// ::test_gelu_small_engine against the bound tests/domain_helpers.py::gelu_bound derives from this formula (x >= 9
+// returns x, -inf returns NaN, the sign never flips); tests/test_domain_inputs_cpu.py::test_gelu_fit_error_in_float64
+// holds the fit figures.  One rcp + one exp2 + 10 FMAs,
 // branch-free: the libm erff costs ~3x as much with both of its branches live in a wave.
 __device__ __forceinline__ float gelu_erf(float x) {
   const float t = __builtin_fabsf(x) * 0.70710678118654752440f;

@@ -50,7 +50,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nb) {
   return base + within;
 }
 
-// same branch-free erf-GELU as the big engine (gemm_split_f16.hip): the two engines must agree
+// same branch-free erf-GELU as the big engine (gemm_split_f16.hip): the two engines must agree - both are held to one
+// per-element bound, this copy by tests/test_domain_gpu.py::test_gelu_small_engine
 __device__ __forceinline__ float gelu_erf(float x) {
   const float t = __builtin_fabsf(x) * 0.70710678118654752440f;
   const float k = __builtin_amdgcn_rcpf(__builtin_fmaf(0.4f, t, 1.0f));
