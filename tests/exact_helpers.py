@@ -246,21 +246,41 @@ def permutation_case(H, W, wh, ww, heads, hd, seed, s=4, min_gap=48.0, max_draws
     return (torch.from_numpy(qkv.reshape(N, 3 * C)), torch.from_numpy(pad.reshape(3 * C)), torch.from_numpy(exp), wins, info)
 
 
+def window_operands(planes, pad_planes, wins, heads):
+    """The pad rule's gather, per window: (idx [L] rows of the extended matrix - N = the pad row -, real [L], the (q, k, v) of
+    the hi plane and of the lo plane as [3, heads, L, hd]).  planes / pad_planes: (hi, lo) of the [N, 3C] matrix and of the
+    pad row (lo zeros for an operand that is not split), on any device."""
+    hi, lo = planes
+    N = hi.shape[0]
+    hd = hi.shape[1] // 3 // heads
+    ext = [torch.cat([p, pp.reshape(1, -1).to(p.device)], 0) for p, pp in zip((hi, lo), pad_planes)]
+    for w in range(wins.tok_of.shape[0]):
+        idx = np.where(wins.tok_of[w] >= 0, wins.tok_of[w], N)
+        ti = torch.from_numpy(idx).to(hi.device)
+        parts = [e[ti].view(-1, 3, heads, hd).permute(1, 2, 0, 3) for e in ext]
+        yield idx, idx < N, parts[0], parts[1]
+
+
 def attention_float64(qkv, pad, wins, heads):
     """Plain float64 windowed attention with the pad rule (pad positions carry q = k = v = pad row, unmasked) -> [H*W, C];
     for the CPU tests of the builders above."""
-    N, C3 = qkv.shape
-    C = C3 // 3
+    N, C = qkv.shape[0], qkv.shape[1] // 3
     hd = C // heads
-    ext = torch.cat([qkv.double(), pad.double()[None]], 0)
     out = torch.zeros(N, C, dtype=torch.float64)
-    for w in range(wins.tok_of.shape[0]):
-        idx = np.where(wins.tok_of[w] >= 0, wins.tok_of[w], N)
-        x = ext[idx].view(-1, 3, heads, hd).permute(1, 2, 0, 3)
+    z, zp = torch.zeros_like(qkv, dtype=torch.float64), torch.zeros_like(pad, dtype=torch.float64)
+    for idx, real, x, _ in window_operands((qkv.double(), z), (pad.double(), zp), wins, heads):
         o = (torch.softmax(x[0] @ x[1].transpose(-1, -2) * hd ** -0.5, -1) @ x[2]).permute(1, 0, 2).reshape(-1, C)
-        real = idx < N
         out[idx[real]] = o[torch.from_numpy(real)]
     return out
+
+
+def plain_rows_of(s):
+    """a plain f16 matrix living in the first half of every row of a split-layout buffer (what the model's workspaces hold in
+    the reduced-precision mode): the hi plane of the SplitMat `s`, as a new SplitMat of the same class"""
+    sm = type(s).empty(s.rows, s.K, s.data.device, zero=True)
+    sm.data[:, : sm.Kp] = s.data.view(s.rows, s.Kp // 32, 2, 32)[:, :, 0].reshape(s.rows, s.Kp)
+    sm.plain = True
+    return sm
 
 
 def ulps(got, exp64):

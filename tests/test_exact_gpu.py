@@ -42,12 +42,7 @@ def _hi_plane(sm):
     return sm.data.view(sm.rows, sm.Kp // 32, 2, 32)[:, :, 0].reshape(sm.rows, sm.Kp)
 
 
-def _plain_rows_of(s):
-    """a plain matrix living in the first half of every row of a split-layout buffer (what the model's workspaces hold)"""
-    sm = ops.SplitMat.empty(s.rows, s.K, s.data.device, zero=True)
-    sm.data[:, : sm.Kp] = _hi_plane(s)
-    sm.plain = True
-    return sm
+_plain_rows_of = X.plain_rows_of
 
 
 def _check_split_output(out_s, e, label):

@@ -183,7 +183,8 @@ def test_window_attention_hd64(dev, ws):
 @pytest.mark.parametrize("ws", [(24, 24), (12, 48), (48, 12), None])
 def test_window_attention_split_f16(dev, ws):
     """f16-split MFMA attention (split qkv in, split out) vs float64; must match the exact-f32
-    kernel's accuracy class."""
+    kernel's accuracy class.  Per element, with derived bounds: tests/test_softmax_gpu.py (this one is an
+    aggregate over all rows)."""
     H, W, C, heads = 72, 144, 128, 2
     g = torch.Generator().manual_seed(11)
     x = torch.randn(1, H * W, C, generator=g)
@@ -233,7 +234,8 @@ def test_global_attention_balanced_schedule(dev):
     tiles' key loops laid end to end and cut into one piece per slot, partial softmaxes merged by attention_merge_kernel)
     at the model's shape, 10 368 tokens x 16 heads: queries of the full pass run the SAME key loop as the plain launch ->
     bit-identical; the others are merged from 2-3 key ranges -> compared with float64, same accuracy class as the plain
-    kernel."""
+    kernel.  Per element, with derived bounds: tests/test_softmax_gpu.py (the key-split tokens are held to an RMSE
+    here)."""
     H, W, C, heads = 72, 144, 1024, 16
     N = H * W
     ok, nb = ops.attention_balanced_plan(N, heads)
@@ -279,7 +281,8 @@ def test_global_attention_balanced_schedule_other_shapes(dev, H, W, heads):
     """Other plans of the balanced schedule on 256 CUs: 7200 tokens x 16 heads (225 wave-tiles = 192 full + 33 in groups
     of 12, 12, 9: a partial last group), 4096 x 32 (8 slots: 96 full + 32), 7680 x 16 (192 + 48), 6144 x 16 (192 full
     tiles exactly: NO key-split part and no workspace), 12 288 x 32 (384 tiles = 4 full passes of 8 slots) - against the
-    plain launch: identical on the full-pass tokens, within fp32 noise on the key-split ones."""
+    plain launch: identical on the full-pass tokens, within fp32 noise on the key-split ones.  The merge's arithmetic per
+    element: tests/test_softmax_gpu.py."""
     C, N = 64 * heads, H * W
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
     if cus != 256:
@@ -311,7 +314,9 @@ def test_global_attention_balanced_schedule_other_shapes(dev, H, W, heads):
 def test_attention_split_softmax_spike(dev, boost):
     """Late dominant key.  boost 4: its score is ~46 log2 units above the running max -> the O / l rescale branch is
     taken; boost 0.5 / 1: ~6 / ~11.5 units -> below / just above the deferral threshold (2^8): below it the running
-    max stays put and that key's p = exp2(s - m) is ~55 (> 1), exact in the hi / lo split."""
+    max stays put and that key's p = exp2(s - m) is ~55 (> 1), exact in the hi / lo split.  The one query that takes the
+    branch is 0.17 % of this RMSE: tests/test_softmax_gpu.py holds every such row to a per-element bound, on either side of
+    the threshold."""
     H, W, C, heads = 8, 72, 64, 1
     N = H * W
     g = torch.Generator().manual_seed(3)
@@ -331,7 +336,8 @@ def test_attention_hi_only_reference_point(dev, case):
     """Reduced-precision attention (hi_only): the exponent's reference point lives in the score MFMA's C operand
     (p = exp2(acc) with Q pre-scaled by scale * log2 e) and is moved by an MFMA when a tile's row sum shows that some p left 2^13 (P_SAFE; the fp32-accurate form defers at 2^8).
     Late dominant keys (as the fp32-accurate twin above), a first tile far BELOW zero (the first tile sets the
-    reference in either direction) and a steady ramp (many small moves) against float64 on the f16-rounded operands."""
+    reference in either direction) and a steady ramp (many small moves) against float64 on the f16-rounded operands.
+    Per element, with derived bounds: tests/test_softmax_gpu.py (this one is an aggregate over all rows)."""
     H, W, C, heads = 8, 72, 64, 1
     N = H * W
     g = torch.Generator().manual_seed(3)
@@ -371,7 +377,8 @@ def test_global_attention_hd72_ragged(dev):
 
 
 def test_attention_softmax_spike(dev):
-    """One key dominates late in the sequence: forces the online-softmax rescale path."""
+    """One key dominates late in the sequence: forces the online-softmax rescale path.  Per element, with derived
+    bounds: tests/test_softmax_gpu.py (this one is an aggregate over all rows)."""
     H, W, C, heads = 8, 72, 64, 1
     N = H * W
     g = torch.Generator().manual_seed(3)
@@ -848,7 +855,7 @@ def test_fused_unembed_in_the_model_equals_the_two_call_form(dev):
 def test_global_attention_balanced_schedule_random_shapes(dev):
     """Randomised plans of the key-split schedule (token counts that leave 0 .. G*12 - 1 remainder tiles, partial last
     groups, 8 / 16 / 32 heads, n_full = 1 .. 3): against the plain launch - identical on the full-pass tokens, fp32 noise
-    on the key-split ones, every token written."""
+    on the key-split ones, every token written.  The merge's arithmetic per element: tests/test_softmax_gpu.py."""
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
     rng = np.random.default_rng(12)
     done = 0
