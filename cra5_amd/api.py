@@ -18,7 +18,9 @@ out).  Conscious differences:
   * a frame with NaN / inf values raises ValueError at the encode edge (the reference would code `int(NaN)`
     garbage silently; masked NetCDF values arrive as NaN);
   * host arrays move through a pinned staging buffer in chunks (csrc/runtime.hip) instead of `.to(device)` /
-    `.cpu()`: `decode_from_bin(..., to_host=True | out=array)` returns the reconstruction as a host array.
+    `.cpu()`: `decode_from_bin(..., to_host=True | out=array)` returns the reconstruction as a host array;
+  * the leg the reference lacks, .bin -> .nc: `decode_to_nc` writes the layout `read_data_from_nc` reads, packed to int16 on
+    the GPU (`pack=` of `decode_from_bin` / `decode_batch`; cra5_amd/pack.py).
 """
 import json
 import os
@@ -29,6 +31,7 @@ import numpy as np
 import torch
 
 from . import binfmt, ops, subset
+from . import pack as _pk
 from . import residual as _res
 from .config import RuntimeConfig, runtime_setting
 from .zoo import vaeformer_pretrained
@@ -523,10 +526,10 @@ class cra5_api:
                                            list(zip(time_stamps, frames)))
 
     def _decode_one(self, i, path, denorm, out=None, sink=None, channels=None, box=None, step=None, coarsen=None,
-                    res_path=None):
+                    res_path=None, pack=None):
         """One frame of the batch decode on the calling frame thread: .bin -> x_hat (or its subset: canonical channels /
         box / step / coarsen of VAEformer._subset_args / _step_arg / _coarsen_arg) -> this thread's pinned buffer -> `sink` / `out[i]` / a fresh
-        array."""
+        array.  pack (_pack_arg): the frame is packed to int16 on this thread's stream first and the codes cross instead."""
         lstrings, shape = self._read_bin(path)
         side = self._residual_load(res_path) if res_path is not None else None
         with torch.no_grad():
@@ -539,6 +542,8 @@ class cra5_api:
             if side is not None:
                 self._residual_correct(x_hat, side, channels, box, step, res_path)
             C, H, W = x_hat.shape[-3:]
+            if pack is not None:
+                return self._decode_one_packed(i, x_hat.reshape(C, H, W), pack, out, sink)
             pin = self.net._pinned("api_x_out", (C, H, W), torch.float32)
             if sink is None and out is not None and self.batch_copy_threads > 1:
                 with self._link("d2h"):
@@ -558,19 +563,87 @@ class cra5_api:
         finally:
             self._log("consume", t_s)
 
-    def _check_out(self, out, n, frame_shape=None):
-        """`out=` of the batch methods: the C memcpy / DMA behind it writes n x C x H x W float32 values (`frame_shape`
-        = (C, H, W): a subset's), so anything else is refused here with a ValueError (not an assert that `python -O`
-        drops - ADVICE r5)."""
+    def _pack_arg(self, what, pack, return_format, meta, per_variable=False):
+        """pack= of the decode methods -> None, or dict(fixed: float64 numpy [C', 2] (pack.resolve_ranges over the decoded
+        channels' names), fixed_dev: the same on the device | None when no range is fixed, groups: None - or, with
+        per_variable, the channel rows of every pressure variable with more than one decoded level: they share one range)."""
+        if pack is None or pack is False:
+            return None
+        if return_format not in ('de_normalized', 'de_normlized'):
+            raise ValueError(f"{what}: pack= packs the de-normalised reconstruction (the ranges are in physical units); "
+                             f"return_format={return_format!r} is not supported with it")
+        names = meta["variables"] if meta is not None else \
+            [self.channels_to_vname.get(c, str(c)) for c in range(self.net.cfg['out_chans'])]
+        fixed = _pk.resolve_ranges(pack, names)
+        groups = None
+        if per_variable:
+            groups = [rows for _, _, rows in _pk.split_variables(names, self.vnames)[0]]
+            for rows in groups:
+                if not np.array_equal(fixed[rows], np.tile(fixed[rows[0]], (len(rows), 1)), equal_nan=True):
+                    raise ValueError(f"{what}: the levels of {names[rows[0]].rsplit('_', 1)[0]!r} go into one NetCDF variable "
+                                     "with one packing - key its range by the variable name, not by a level")
+            groups = [rows for rows in groups if len(rows) > 1 and np.isnan(fixed[rows[0], 0])]
+        dev = None
+        if not np.isnan(fixed[:, 0]).all():
+            dev = torch.from_numpy(fixed).to(self.net.device)
+            torch.cuda.current_stream().synchronize()       # read by every frame thread's stream
+        return dict(fixed=fixed, fixed_dev=dev, groups=groups or None)
+
+    def _pack_device(self, x, pk, q_out=None, table_out=None):
+        """Pack the device frame x [C', H, W] on the current stream -> (q int16 device, table fp64 device [C', 5], the
+        fixed ranges used: float64 numpy [C', 2]).  With pk["groups"] the rows of a group get the group's own (min of
+        vmin, max of vmax) as their fixed range: a first range pass, C' x 2 doubles to the host and back, a second one."""
+        table = ops.pack_range(x, pk["fixed_dev"], out=table_out)
+        fixed = pk["fixed"]
+        if pk["groups"]:
+            mm = table[:, :2].cpu().numpy()
+            fixed = fixed.copy()
+            for rows in pk["groups"]:
+                fixed[rows] = (np.fmin.reduce(mm[rows, 0]), np.fmax.reduce(mm[rows, 1]))    # (NaN: no finite value at all)
+            table = ops.pack_range(x, torch.from_numpy(fixed).to(x.device), out=table)
+        return ops.pack_i16(x, table, out=q_out), table, fixed
+
+    def _decode_one_packed(self, i, x, pk, out, sink):
+        """_decode_one's way out with pack=: x [C', H, W] on the device -> codes and table through this thread's pinned
+        buffers in ONE turn on the link (half the bytes of the fp32 frame) -> the dict of pack.pack_frame, q a host array."""
+        shape = tuple(x.shape)
+        q, table, fixed = self._pack_device(x, pk, q_out=self.net._buf("api_q_dev", shape, torch.int16),
+                                            table_out=self.net._buf("api_pack_table", (shape[0], len(ops.PACK_FIELDS)),
+                                                                    torch.float64))
+        pin = self.net._pinned("api_q_out", shape, torch.int16)
+        tpin = self.net._pinned("api_pack_table_out", tuple(table.shape), torch.float64)
+        with self._link("d2h"):
+            pin.copy_(q, non_blocking=True)
+            tpin.copy_(table, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        t_s = time.perf_counter()
+        try:
+            item = _pk.frame_stats(tpin.numpy(), fixed)
+            if sink is not None:
+                item["q"] = pin.numpy()
+                return sink(i, item)
+            if out is not None:
+                np.copyto(out[i], pin.numpy())
+                item["q"] = out[i]
+            else:
+                item["q"] = pin.numpy().copy()
+            return item
+        finally:
+            self._log("consume", t_s)
+
+    def _check_out(self, out, n, frame_shape=None, dtype=np.float32):
+        """`out=` of the batch methods: the C memcpy / DMA behind it writes n x C x H x W values of `dtype` (float32; int16
+        with pack=) (`frame_shape` = (C, H, W): a subset's), so anything else is refused here with a ValueError (not an
+        assert that `python -O` drops - ADVICE r5)."""
         if out is None:
             return
         C = self.net.cfg['out_chans']
         H, W = self.net.cfg['img_size']
         if frame_shape is not None:
             C, H, W = frame_shape
-        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or tuple(out.shape) != (n, C, H, W) \
+        if not isinstance(out, np.ndarray) or out.dtype != dtype or tuple(out.shape) != (n, C, H, W) \
                 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
-            raise ValueError(f"`out` must be a writeable C-contiguous float32 numpy array of shape [{n}, {C}, {H}, {W}]"
+            raise ValueError(f"`out` must be a writeable C-contiguous {np.dtype(dtype).name} numpy array of shape [{n}, {C}, {H}, {W}]"
                              f" (got {type(out).__name__} {getattr(out, 'dtype', None)} {getattr(out, 'shape', None)})")
 
     def roundtrip_batch(self, time_stamps, data=None, save_root=None, workers=12, sink=None, out=None,
@@ -594,7 +667,7 @@ class cra5_api:
         return self._pipeline(workers).map(one, [(i, ts, a) for i, (ts, a) in enumerate(zip(time_stamps, frames))])
 
     def decode_batch(self, time_stamps=None, paths=None, return_format='de_normalized', out=None, workers=12, sink=None,
-                     variables=None, region=None, stride=None, coarsen=None, residual=None):
+                     variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None):
         """decode_from_bin for many frames.  Returns a list of HOST float32 arrays [C, H, W] (views of `out`
         [n, C, H, W] when given, fresh arrays otherwise); the D2H of each reconstruction goes through the
         decoding thread's pinned buffer and overlaps the other frames' work.  `sink(i, frame)`: called on the decoding
@@ -608,7 +681,18 @@ class cra5_api:
         cell - 1 / (k_lat * k_lon) of the bytes cross the host link; grid_box(region, coarsen=coarsen) gives lat / lon
         and the cells' lat_bnds / lon_bnds.
         residual (decode_from_bin): True - the .res beside every .bin -, or one sidecar path per frame; every frame is
-        corrected on the device before it crosses the host link."""
+        corrected on the device before it crosses the host link.
+        pack (decode_from_bin; only with return_format 'de_normalized'): "int16" / True / {variable: (lo, hi)} - every frame
+        is packed to int16 on its own stream right after decode and residual (cra5_amd.pack, DESIGN.md section 4 "Packed
+        int16 output"); the codes and the [C', 5] table cross the link in one turn through an int16 pinned buffer, half the
+        bytes of the fp32 copy.  Every list item is then the dict of pack.pack_frame - q (a host int16 array [C', Hb, Wb]),
+        scale_factor, add_offset, vmin, vmax, nonfinite, saturated, fill_value; `out` must be a C-contiguous int16 array
+        [n, C', Hb, Wb] and q is its view; `sink(i, item)` receives the dict, q a view of the pinned buffer."""
+        return self._decode_batch(time_stamps, paths, return_format, out, workers, sink, variables, region, stride, coarsen,
+                                  residual, pack)
+
+    def _decode_batch(self, time_stamps, paths, return_format, out, workers, sink, variables, region, stride, coarsen,
+                      residual, pack, what="decode_batch", per_variable=False):
         if paths is None:
             paths = [f'{self.local_root}/CRA5/{ts[:4]}/{ts}.bin' for ts in time_stamps]
         if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
@@ -616,15 +700,54 @@ class cra5_api:
         denorm = return_format != 'normalized'
         self.net._require_gpu()
         channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
-        sides = self._residual_arg("decode_batch", residual, list(paths), return_format, sel["coarsen"])
+        sides = self._residual_arg(what, residual, list(paths), return_format, sel["coarsen"])
+        pk = self._pack_arg(what, pack, return_format, meta, per_variable)
         shape = None
         if meta is not None:
             shape = (len(meta["variables"]), len(meta["lat"]), len(meta["lon"]))
-        self._check_out(out, len(paths), shape)
+        self._check_out(out, len(paths), shape, np.int16 if pk is not None else np.float32)
 
         return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box,
-                                                                       res_path=sides[it[0]], **sel),
+                                                                       res_path=sides[it[0]], pack=pk, **sel),
                                            list(enumerate(paths)))
+
+    def decode_to_nc(self, time_stamps=None, paths=None, save_root=None, pack="int16", variables=None, region=None,
+                     stride=None, coarsen=None, residual=None, workers=12):
+        """.bin archives back to the NetCDF files the rest of the tool chain reads: decode_batch(pack=...) with a sink that
+        writes every frame, on its decoding thread, as {save_root}/ERA5/{yyyy}/{ts}_pressure.nc / {ts}_single.nc in the
+        layout read_data_from_nc reads (pack.write_era5_nc: NetCDF-3 64-bit offset, int16 with scale_factor / add_offset /
+        _FillValue per variable, a file without a selected variable is not written).  save_root: default local_root.
+        The file names come from time_stamps (needed also with paths=).
+        A NetCDF variable has one packing, so the decoded levels of one pressure variable share one range per frame:
+        ops.pack_range measures every channel on the device, the variable's (min of vmin, max of vmax) - C' x 2 doubles on
+        the host - becomes the fixed range of its levels, and the packing proceeds as for any fixed range.
+        pack: "int16" (those per-frame ranges) or {name: (lo, hi)} fixed physical ranges; a name is the NETCDF VARIABLE
+        name for a pressure variable ("z": every decoded level of z; a single level such as "z_500" is refused) or the
+        channel name of a single-level variable ("t2m"; "tp" in the model's tp x 1000).  The pressure selection must be
+        rectangular - every selected pressure variable with the same levels in the same order (ValueError, before any
+        decode).  variables / region / stride / coarsen / residual: as in decode_batch.
+        Returns one dict per frame: time_stamp, files (the paths written), bytes (their total size)."""
+        if time_stamps is None:
+            raise ValueError("decode_to_nc needs time_stamps: they name the NetCDF files")
+        time_stamps = list(time_stamps)
+        if paths is not None and len(list(paths)) != len(time_stamps):
+            raise ValueError("decode_to_nc: time_stamps and paths must have the same length")
+        save_root = save_root or self.local_root
+        _, _, _, meta = self._subset(variables, region, stride, coarsen)
+        if meta is None:
+            H, W = self.net.cfg['img_size']
+            g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W)
+            meta = dict(variables=[self.channels_to_vname.get(c, str(c)) for c in range(self.net.cfg['out_chans'])],
+                        lat=g["lat"], lon=g["lon"])
+        names, lat, lon = meta["variables"], meta["lat"], meta["lon"]
+
+        def sink(i, item):
+            t0 = time.perf_counter()
+            files = _pk.write_era5_nc(save_root, time_stamps[i], item, names, lat, lon, self.vnames)
+            self._log("write_nc", t0)
+            return dict(time_stamp=time_stamps[i], files=files, bytes=sum(os.path.getsize(p) for p in files))
+        return self._decode_batch(time_stamps, paths, 'de_normalized', None, workers, sink, variables, region, stride,
+                                  coarsen, residual, pack, what="decode_to_nc", per_variable=True)
 
     def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, coarsen=None, spectrum=False, tol=None):
         """One frame of evaluate_batch on the calling frame thread: the truth is staged once into this thread's device
@@ -1016,7 +1139,7 @@ class cra5_api:
             return self.net.decode_latent(y_hat, channels=channels, box=box, **sel)
 
     def decode_from_bin(self, time_stamp=None, custom_path=None, return_format='de_normalized', to_host=False, out=None,
-                        variables=None, region=None, stride=None, coarsen=None, residual=None):
+                        variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None):
         """cra5_api.py:153-192.  `to_host=True` (or `out=` a float32 array of the frame's shape): `x_hat` comes back
         as a HOST numpy array through the pinned staging buffer instead of a device tensor.
         variables: names of channel_vname_mapping() (e.g. ["z_500", "t_850", "t2m"]), output channels in that order;
@@ -1041,7 +1164,17 @@ class cra5_api:
         bit for bit or within the sidecar's tolerance of it, and a variables / region / stride subset is the slice of the
         corrected full frame, bit for bit.  The sidecar's witness points that fall inside the decoded subset are compared
         with the plain decode first (those outside it are not checked): a difference raises ResidualMismatchError and
-        nothing is corrected.  Only with return_format 'de_normalized' and without coarsen= (ValueError otherwise)."""
+        nothing is corrected.  Only with return_format 'de_normalized' and without coarsen= (ValueError otherwise).
+        pack: None | "int16" / True (every channel packed over its own range in this frame - of the decoded subset, so a
+        region's codes are not the slice of the globe's) | {variable: (lo, hi)} (pack.resolve_ranges: a fixed physical
+        range for those channels, keyed by channel name or by pressure variable; under a fixed range a region's codes ARE
+        the slice of the globe's, bit for bit).  `x_hat` is then the int16 frame [C', Hb, Wb] packed on the GPU (DESIGN.md
+        section 4, "Packed int16 output") - a device tensor, or with to_host=True / out= an int16 array a host array - and
+        the dict gains scale_factor, add_offset (float64 [C']), fill_value (-32768, the code of a non-finite value), vmin,
+        vmax (float32), nonfinite (int64), saturated (bool: values outside a fixed range took -+32767).  unpack(q) = q *
+        scale_factor + add_offset is within scale_factor * (0.5 + 2^-30) + 2^-50 max(|lo|, |hi|) of the decoded value; with
+        residual=True the frame is corrected first and then packed, and the distance to the truth is bounded by the
+        sidecar's tolerance plus that packing bound.  Only with return_format 'de_normalized' (ValueError otherwise)."""
         if return_format == 'latent' and (variables is not None or region is not None or stride is not None
                                           or coarsen is not None):
             raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region / stride / "
@@ -1052,6 +1185,8 @@ class cra5_api:
         bin_path = custom_path or f'{self.local_root}/CRA5/{time_stamp[:4]}/{time_stamp}.bin'
         res_path = self._residual_arg("decode_from_bin", residual if residual is None or isinstance(residual, bool) else [residual],
                                       [bin_path], return_format, sel["coarsen"])[0]
+        pk = self._pack_arg("decode_from_bin", pack, return_format, meta)
+        stats = None
         decoding_start = time.time()
         lstrings, shape = self._read_bin(bin_path)
         side = self._residual_load(res_path) if res_path is not None else None
@@ -1067,16 +1202,22 @@ class cra5_api:
                                                  box=box, **sel)
                 if side is not None:
                     self._residual_correct(x_hat, side, channels, box, sel["step"], res_path)
+            ht, dt = (np.float32, torch.float32) if pk is None else (np.int16, torch.int16)
+            if pk is not None:
+                x_hat, table, fixed = self._pack_device(x_hat.reshape(x_hat.shape[-3:]), pk)
+                stats = _pk.frame_stats(table.cpu().numpy(), fixed)
             if to_host or out is not None:
                 src = x_hat.reshape(x_hat.shape[-3:]).contiguous()
                 if out is None:
-                    out = np.empty(tuple(src.shape), dtype=np.float32)
-                if out.dtype != np.float32 or tuple(out.shape) != tuple(src.shape) or not out.flags["C_CONTIGUOUS"]:
-                    raise ValueError("`out` must be a C-contiguous float32 array of shape %r" % (tuple(src.shape),))
-                pin = self.net._pinned("api_x_out", tuple(src.shape), torch.float32)
+                    out = np.empty(tuple(src.shape), dtype=ht)
+                if out.dtype != ht or tuple(out.shape) != tuple(src.shape) or not out.flags["C_CONTIGUOUS"]:
+                    raise ValueError("`out` must be a C-contiguous %s array of shape %r" % (np.dtype(ht).name, tuple(src.shape)))
+                pin = self.net._pinned("api_x_out" if pk is None else "api_q_out", tuple(src.shape), dt)
                 x_hat = ops.copy_d2h_staged(out, src, pin, threads=self.runtime.copy_threads)
         torch.cuda.synchronize()
         res = dict(x_hat=x_hat, decoding_time=time.time() - decoding_start)
         if meta is not None:
             res.update(meta)
+        if stats is not None:
+            res.update(stats)
         return res

@@ -771,6 +771,60 @@ def recon_error(x_hat, x, lat_w=None, out=None):
     return out
 
 
+PACK_FIELDS = ("vmin", "vmax", "nonfinite", "scale", "offset")   # CRA5_PACK_* order
+
+
+def _pack_frame(what, x):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+        raise TypeError(f"{what} takes a contiguous fp32 device tensor [C, H, W]")
+    if x.dim() != 3 or x.numel() == 0 or x.shape[1] * x.shape[2] >= 1 << 31:
+        raise ValueError(f"{what}: x {tuple(x.shape)} must be a non-empty [C, H, W] with H * W < 2^31")
+    return int(x.shape[0]), int(x.shape[1] * x.shape[2])
+
+
+def _pack_f64(what, name, t, shape, device):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+        raise TypeError(f"{what}: {name} must be a contiguous fp64 device tensor {list(shape)}")
+    if tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError(f"{what}: {name} must be {list(shape)} on the frame's device, got {tuple(t.shape)} on {t.device}")
+
+
+def pack_range(x, fixed=None, out=None):
+    """cra5_pack_range_f32: per channel of the contiguous fp32 device frame x [C, H, W] the min / max of its finite
+    elements, the count of the others and the int16 packing's scale / offset ("Packed int16 output")
+    -> fp64 device tensor [C, len(PACK_FIELDS)] (`out`), in the fields of PACK_FIELDS.  fixed: fp64 device [C, 2] (lo, hi)
+    or None; a row whose lo is NaN takes the frame's own range, any other row must be finite with lo < hi (the caller's
+    duty: pack.resolve_ranges checks it on the host).  On the current stream; the slab of partials comes from torch's
+    caching allocator."""
+    C, plane = _pack_frame("pack_range", x)
+    if fixed is not None:
+        _pack_f64("pack_range", "fixed", fixed, (C, 2), x.device)
+    if out is None:
+        out = torch.empty((C, len(PACK_FIELDS)), device=x.device, dtype=torch.float64)
+    else:
+        _pack_f64("pack_range", "out", out, (C, len(PACK_FIELDS)), x.device)
+    nb = lib().cra5_pack_range_slab_bytes(C, plane)
+    slab = torch.empty((nb // 8,), device=x.device, dtype=torch.float64)
+    check(lib().cra5_pack_range_f32(_p(x), C, plane, _p(fixed), _p(slab), nb, _p(out), _stream()), "cra5_pack_range_f32")
+    return out
+
+
+def pack_i16(x, table, out=None):
+    """cra5_pack_i16_f32: the int16 codes of the contiguous fp32 device frame x [C, H, W] under the scale / offset of
+    `table` (pack_range's fp64 device [C, len(PACK_FIELDS)]) -> int16 device tensor shaped like x (`out`): -32768 for a
+    non-finite x, else clamp(rint((double(x) - offset) / scale), -32767, 32767).  On the current stream."""
+    C, plane = _pack_frame("pack_i16", x)
+    _pack_f64("pack_i16", "table", table, (C, len(PACK_FIELDS)), x.device)
+    if out is None:
+        out = torch.empty(tuple(x.shape), device=x.device, dtype=torch.int16)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int16 and out.is_contiguous()):
+        raise TypeError(f"pack_i16: out must be a contiguous int16 device tensor {list(x.shape)}")
+    elif tuple(out.shape) != tuple(x.shape) or out.device != x.device:
+        raise ValueError(f"pack_i16: out must be {list(x.shape)} on the frame's device, got {tuple(out.shape)} on {out.device}")
+    check(lib().cra5_pack_i16_f32(_p(x), C, plane, _p(table), _p(out), _stream()), "cra5_pack_i16_f32")
+    return out
+
+
 SPECTRUM_MAX_W = 1440    # CRA5_SPECTRUM_MAX_W
 _TWIDDLES = {}           # (W, device) -> fp64 device [W, 2]: (cos, sin) of -2 pi j / W
 

@@ -349,6 +349,38 @@ size_t cra5_recon_error_slab_bytes(int C, int H, int W);
 int cra5_recon_error_f32(const float *x_hat, const float *x, int C, int H, int W, const float *lat_w, double *slab,
                          size_t slab_bytes, double *out, void *stream);
 
+/* Packed int16 output (csrc/pack.hip; DESIGN.md section 4, "Packed int16 output").  x [C][plane] fp32, contiguous,
+ * 4-byte aligned (a 16-byte aligned base and plane % 4 == 0 are not needed).  Per channel c:
+ *   an element is finite when its exponent bits are not all ones; NONFINITE = the count of the others; VMIN / VMAX = the
+ *   fp32 min / max over the finite elements (exact; NaN when there are none; of +0 and -0 either may be reported);
+ *   range (lo, hi) in float64 = fixed[c] when `fixed` is given and fixed[c][0] is not NaN (the caller guarantees finite
+ *   lo < hi), else ((double)VMIN, (double)VMAX);
+ *   no finite element and no fixed range: SCALE = 1, OFFSET = 0;  lo == hi: SCALE = 1, OFFSET = lo;  otherwise
+ *   SCALE = (hi - lo) / 65534.0 and OFFSET = (lo + hi) * 0.5, in IEEE float64.
+ * cra5_pack_range_f32 writes out [C][CRA5_PACK_FIELDS] fp64 (VMIN, VMAX, NONFINITE, SCALE, OFFSET).  fixed: device fp64
+ * [C][2] or NULL.  `slab`: caller-owned device scratch of >= cra5_pack_range_slab_bytes(C, plane) bytes, 16-byte aligned
+ * (one record per block, overwritten: no memset, no atomics).  Two launches on `stream`, fixed reduction order: the table
+ * is bit-identical from run to run.
+ * cra5_pack_i16_f32 reads SCALE / OFFSET of such a table (device, [C][CRA5_PACK_FIELDS]) and writes q [C][plane] int16
+ * (2-byte aligned), nothing outside it: a non-finite x gives CRA5_PACK_FILL, any other
+ *   q = (int16) clamp(rint(((double)x - OFFSET) / SCALE), -32767, 32767),
+ * the subtraction and a true division in float64, rint to nearest-even, the clamp in float64 before the conversion.
+ * unpack(q) = (double)q * SCALE + OFFSET; for every finite x inside (lo, hi):
+ *   |unpack(q) - x| <= SCALE * (0.5 + 2^-30) + 2^-50 * max(|lo|, |hi|).
+ * slab_bytes returns 0 and the launchers CRA5_ERR_ARG, before any device work, for C <= 0, plane == 0 or >= 2^31, NULL
+ * (fixed may be NULL) or misaligned pointers and a slab that is too small. */
+#define CRA5_PACK_FIELDS 5
+#define CRA5_PACK_VMIN 0
+#define CRA5_PACK_VMAX 1
+#define CRA5_PACK_NONFINITE 2
+#define CRA5_PACK_SCALE 3
+#define CRA5_PACK_OFFSET 4
+#define CRA5_PACK_FILL (-32768)
+size_t cra5_pack_range_slab_bytes(int C, size_t plane);
+int cra5_pack_range_f32(const float *x, int C, size_t plane, const double *fixed, void *slab, size_t slab_bytes,
+                        double *out, void *stream);
+int cra5_pack_i16_f32(const float *x, int C, size_t plane, const double *table, int16_t *q, void *stream);
+
 /* Zonal power spectra of a frame pair (csrc/spectrum.hip): x_hat, x [C][H][W] fp32, d = x_hat - x in
  * fp32.  For a row f(c, h, .):  F(c, h, k) = sum_w f(c, h, w) e^(-2 pi i k w / W),  k = 0 .. K - 1,  K = W / 2 + 1, and
  *   P_f(c, k) = (1 / H) sum_h L(h) m_k |F(c, h, k)|^2 / W^2,   m_k = 1 for k = 0 and for k = W / 2 of an even W, else 2,
