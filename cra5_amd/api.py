@@ -22,10 +22,13 @@ out).  Conscious differences:
   * the leg the reference lacks, .bin -> .nc: `decode_to_nc` writes the layout `read_data_from_nc` reads, packed to int16 on
     the GPU (`pack=` of `decode_from_bin` / `decode_batch`; cra5_amd/pack.py).
 """
+import contextlib
 import json
 import os
+import threading
 import time
 from pathlib import Path
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -78,6 +81,34 @@ def variable_mapping(config=None):
     return _channel_mapping(vnames, pressure_level)
 
 
+class Selection(NamedTuple):
+    """What one decode returns of the frame (cra5_api._select): the model's canonical arguments and the grid they leave."""
+    channels: Optional[tuple]       # canonical (VAEformer._selection_args): None = every channel / the globe / no
+    box: Optional[tuple]            # thinning / no coarsening
+    step: Optional[tuple]
+    coarsen: Optional[tuple]
+    names: list                     # of the decoded channels, in their order - for the whole grid too
+    lat: np.ndarray                 # float64 coordinates of the decoded rows / columns
+    lon: np.ndarray
+    lat_bnds: Optional[np.ndarray]  # the coarse cells' edges; None without coarsen
+    lon_bnds: Optional[np.ndarray]
+    shape: tuple                    # (C', Hb, Wb) of one decoded frame
+    whole: bool                     # no argument asked for a subset: decode_from_bin's dict carries no extra keys
+
+    @property
+    def model(self):
+        """The keyword arguments of _decompress_frame / _decode_guarded / decode_latent."""
+        return dict(channels=self.channels, box=self.box, step=self.step, coarsen=self.coarsen)
+
+    @property
+    def meta(self):
+        """The result dicts' keys: variables, lat, lon - with coarsen also coarsen, lat_bnds, lon_bnds."""
+        meta = dict(variables=self.names, lat=self.lat, lon=self.lon)
+        if self.coarsen is not None:
+            meta.update(coarsen=self.coarsen, lat_bnds=self.lat_bnds, lon_bnds=self.lon_bnds)
+        return meta
+
+
 class cra5_api:
     def __init__(self, config=None, local_root=None, device=None, ceph_cfg=None, weights=None, quality=268, runtime=None):
         self.device = device or ('cuda' if torch.cuda.is_available() else 'cpu')
@@ -94,7 +125,6 @@ class cra5_api:
         self.local_root = local_root or f'{os.getcwd()}/data'
         # settings: ONE RuntimeConfig (cra5_amd/config.py); batch_copy_threads / link_serial are properties over it
         self.runtime = runtime if runtime is not None else (getattr(weights, "runtime", None) or RuntimeConfig.from_env())
-        import threading
         self._link_gate = {"h2d": threading.Lock(), "d2h": threading.Lock()}
         self.phase_log = None       # a list: (frame tag, phase, t_start, t_end) per batch-path phase (tools/api_phase_probe.py)
         self._era5 = None
@@ -197,6 +227,17 @@ class cra5_api:
             raise ValueError("the input frame holds NaN / inf values (masked NetCDF values are read as NaN): fill them "
                              "before encoding - the codec would turn them into arbitrary symbols")
 
+    def _checked(self, frame, run):
+        """-> run(), the encode of `frame`, between the launch of the frame's finiteness probe and its verdict."""
+        probe = self._finite_probe(frame)
+        try:
+            res = run()
+        except FloatingPointError:
+            self._require_finite(probe)     # a non-finite INPUT is the caller's ValueError
+            raise
+        self._require_finite(probe)
+        return res
+
     def channel_vname_mapping(self):
         """cra5_api.py:228-241."""
         return _channel_mapping(self.vnames, self.pressure_level)
@@ -216,22 +257,21 @@ class cra5_api:
     grid_box = staticmethod(subset.grid_box)
     resolve_variables = staticmethod(subset.resolve_variables)
 
-    def _subset(self, variables, region, stride=None, coarsen=None):
-        """-> (channel indices | None, grid box | None, dict(step=(s_lat, s_lon) | None, coarsen=(k_lat, k_lon) | None) -
-        the model's keyword arguments -, the result dict's extra keys); (None, None, both None, None) without a subset."""
+    def _names(self, chans=None):
+        """The names of the channels `chans`, in that order; None: of every channel of the model."""
+        return [self.channels_to_vname.get(c, str(c)) for c in (chans if chans is not None else range(self.net.cfg['out_chans']))]
+
+    def _select(self, variables=None, region=None, stride=None, coarsen=None):
+        """The arguments of the decode methods -> their Selection; without any of them the whole grid's."""
         H, W = self.net.cfg['img_size']
         step, k = subset._stride_or_coarsen(stride, coarsen, H, W)
-        if variables is None and region is None and step is None and k is None:
-            return None, None, dict(step=None, coarsen=None), None
+        whole = variables is None and region is None and step is None and k is None
         chans = subset.resolve_variables(variables, self.vname_to_channels)
         g = subset.grid_box(region if region is not None else (-90.0, 90.0, 0.0, 360.0), H, W, stride=step, coarsen=k)
-        names = [self.channels_to_vname.get(c, str(c)) for c in (chans if chans is not None else range(self.net.cfg['out_chans']))]
-        channels, box = self.net._subset_args(chans, g["box"] if region is not None else None)
-        meta = dict(variables=names, lat=g["lat"], lon=g["lon"])
-        if k is not None:
-            meta.update(coarsen=k, lat_bnds=g["lat_bnds"], lon_bnds=g["lon_bnds"])
-        step = self.net._step_arg(step, box)
-        return channels, box, dict(step=step, coarsen=self.net._coarsen_arg(k, box, step)), meta
+        names = self._names(chans)
+        channels, box, step, k = self.net._selection_args(chans, g["box"] if region is not None else None, step, k)
+        return Selection(channels, box, step, k, names, g["lat"], g["lon"], g.get("lat_bnds"), g.get("lon_bnds"),
+                         (len(names), len(g["lat"]), len(g["lon"])), whole)
 
     def get_mean_std(self):
         """cra5_api.py:243-261."""
@@ -261,17 +301,26 @@ class cra5_api:
             self.net._require_gpu()
             return self.net._encode_y_guarded(frame, mean=self._mean_flat, std=self._std_flat)
 
+    def _compress_output(self, frame):
+        """One physical-units device frame -> the `output` dict of the encode methods: its two strings and z_shape."""
+        y_str, z_str = self.net._compress_frame(x=frame, mean=self._mean_flat, std=self._std_flat)
+        return {"strings": [[y_str], [z_str]], "z_shape": torch.Size([self.net.Hz, self.net.Wz])}
+
+    @staticmethod
+    def _write_bin(save_root, ts, output, write=True):
+        """-> {save_root}/{yyyy}/{ts}.bin, the path of the frame's archive file; written unless write is False."""
+        path = f'{save_root}/{ts.split("-")[0]}/{ts}.bin'
+        if write:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with Path(path).open("wb") as f:
+                binfmt.write_bin(f, output["strings"], output["z_shape"])
+        return path
+
     def encode_to_latent(self, time_stamp=None, save_root=None, latent_type='float', data=None):
         """cra5_api.py:53-71."""
         frame = self._frame(time_stamp, data)
         with torch.no_grad():
-            probe = self._finite_probe(frame)
-            try:
-                y = self._encode_y(frame)
-            except FloatingPointError:
-                self._require_finite(probe)     # a non-finite INPUT is the caller's ValueError
-                raise
-            self._require_finite(probe)
+            y = self._checked(frame, lambda: self._encode_y(frame))
             if latent_type == 'float':
                 return y.unsqueeze(0)
             if latent_type == 'quantized':
@@ -293,41 +342,24 @@ class cra5_api:
         corrections than max_fraction of the corrected channels' points raise ResidualBudgetError, no .res is written."""
         save_root = save_root or self.local_root
         tol = self._residual_tol(max_error)
-        if tol is not None and return_format in ('latent', 'quantized'):
-            raise ValueError(f"encode_era5_as_bin: max_error writes a sidecar beside the .bin; return_format={return_format!r} "
-                             "writes none")
+        if return_format in ('latent', 'quantized'):
+            if tol is not None:
+                raise ValueError(f"encode_era5_as_bin: max_error writes a sidecar beside the .bin; return_format="
+                                 f"{return_format!r} writes none")
+            return self.encode_to_latent(time_stamp, latent_type='float' if return_format == 'latent' else 'quantized',
+                                         data=data)
         st1 = time.time()
         frame = self._frame(time_stamp, data)
         st2 = time.time()
         with torch.no_grad():
-            probe = self._finite_probe(frame)
-            try:
-                if return_format in ('latent', 'quantized'):
-                    y = self._encode_y(frame)
-                else:
-                    # g_a and the latent side as ONE GPU phase (what the batch path runs: the same kernels on the same
-                    # values, the same bytes - no stream sync and host round trip between the two halves)
-                    self.net._require_gpu()
-                    y_str, z_str = self.net._compress_frame(x=frame, mean=self._mean_flat, std=self._std_flat)
-            except FloatingPointError:
-                self._require_finite(probe)     # a non-finite INPUT is the caller's ValueError
-                raise
-            self._require_finite(probe)
-            if return_format == 'latent':
-                return y.unsqueeze(0)
-            if return_format == 'quantized':
-                s = self.net._latent_side_guarded(y)
-                return s["y_hat"].reshape(y.shape).unsqueeze(0)
-            output = {"strings": [[y_str], [z_str]], "z_shape": torch.Size([self.net.Hz, self.net.Wz])}
-            year = time_stamp.split('-')[0]
-            file_url = f'{save_root}/{year}/{time_stamp}.bin'
+            # g_a and the latent side as ONE GPU phase (what the batch path runs: the same kernels on the same
+            # values, the same bytes - no stream sync and host round trip between the two halves)
+            output = self._checked(frame, lambda: self._compress_output(frame))
             side = None
             if tol is not None:
-                side = self._residual_encode(time_stamp, frame, y_str, z_str, output["z_shape"], tol, max_fraction)
+                side = self._residual_encode(time_stamp, frame, output, tol, max_fraction)
         st3 = time.time()
-        os.makedirs(os.path.dirname(file_url), exist_ok=True)
-        with Path(file_url).open("wb") as f:
-            binfmt.write_bin(f, output["strings"], output["z_shape"])
+        file_url = self._write_bin(save_root, time_stamp, output)
         res = dict(output=output, save_path=file_url)
         if side is not None:
             res["residual"] = self._residual_write(side, file_url)
@@ -442,40 +474,32 @@ class cra5_api:
 
     def _log(self, phase, t0):
         if self.phase_log is not None:
-            import threading
             self.phase_log.append((threading.get_ident(), phase, t0, time.perf_counter()))
 
+    @contextlib.contextmanager
     def _link(self, direction):
         """Context manager: this thread's turn on the host link in `direction` ("h2d" / "d2h"); logs wait + transfer."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def turn():
-            t0 = time.perf_counter()
+        t0 = time.perf_counter()
+        if self.link_serial:
+            self._link_gate[direction].acquire()
+        t1 = time.perf_counter()
+        try:
+            yield
+        finally:
             if self.link_serial:
-                self._link_gate[direction].acquire()
-            t1 = time.perf_counter()
-            try:
-                yield
-            finally:
-                if self.link_serial:
-                    self._link_gate[direction].release()
-                if self.phase_log is not None:
-                    import threading
-                    self.phase_log.append((threading.get_ident(), direction + "_wait", t0, t1))
-                    self.phase_log.append((threading.get_ident(), direction, t1, time.perf_counter()))
-        return turn()
+                self._link_gate[direction].release()
+            if self.phase_log is not None:
+                self.phase_log.append((threading.get_ident(), direction + "_wait", t0, t1))
+                self.phase_log.append((threading.get_ident(), direction, t1, time.perf_counter()))
 
     def _encode_one(self, ts, arr, save_root, write=True, tol=None, max_fraction=None):
         """One frame of the batch encode on the calling frame thread (its stream, its pinned / device buffers).  tol
         (float32 [C], _residual_tol): the thread then decodes its own strings and writes the residual sidecar."""
         enc, x = self._encode_staged(ts, arr, save_root, write)
         if tol is not None:
-            out = enc["output"]
             t0 = time.time()
             with torch.no_grad():
-                side = self._residual_encode(ts, x, out["strings"][0][0], out["strings"][1][0], out["z_shape"], tol,
-                                             max_fraction)
+                side = self._residual_encode(ts, x, enc["output"], tol, max_fraction)
             enc["residual"] = self._residual_write(side, enc["save_path"], write)
             enc["encoding_time"] += time.time() - t0
         return enc
@@ -489,25 +513,16 @@ class cra5_api:
         t1 = time.time()
         with torch.no_grad():
             x = self._stage_in(arr)
-            probe = self._finite_probe(x)
-            # the frame has landed BEFORE this thread queues for a GPU-phase slot: a slot held while its stream waits 20 ms
-            # for the PCIe transfer is a third of the chip's concurrency gone (encode_era5_batch: 38 -> frames/s)
-            torch.cuda.current_stream().synchronize()
-            t_c = time.perf_counter()
-            try:
-                y_str, z_str = self.net._compress_frame(x=x, mean=self._mean_flat, std=self._std_flat)
-            except FloatingPointError:
-                self._require_finite(probe)     # a non-finite INPUT is the caller's ValueError, as before
-                raise
-            self._require_finite(probe)
+
+            def run():
+                # the frame has landed BEFORE this thread queues for a GPU-phase slot: a slot held while its stream waits
+                # 20 ms for the PCIe transfer is a third of the chip's concurrency gone (encode_era5_batch: 38 -> frames/s)
+                torch.cuda.current_stream().synchronize()
+                return time.perf_counter(), self._compress_output(x)
+            t_c, output = self._checked(x, run)
             self._log("compress", t_c)
-        output = {"strings": [[y_str], [z_str]], "z_shape": torch.Size([self.net.Hz, self.net.Wz])}
         t2 = time.time()
-        file_url = f'{save_root}/{ts.split("-")[0]}/{ts}.bin'
-        if write:
-            os.makedirs(os.path.dirname(file_url), exist_ok=True)
-            with Path(file_url).open("wb") as f:
-                binfmt.write_bin(f, output["strings"], output["z_shape"])
+        file_url = self._write_bin(save_root, ts, output, write)
         return dict(output=output, reading_time=t1 - t0, encoding_time=t2 - t1, saving_time=time.time() - t2,
                     save_path=file_url), x
 
@@ -525,45 +540,71 @@ class cra5_api:
         return self._pipeline(workers).map(lambda it: self._encode_one(it[0], it[1], save_root, write, tol, max_fraction),
                                            list(zip(time_stamps, frames)))
 
-    def _decode_one(self, i, path, denorm, out=None, sink=None, channels=None, box=None, step=None, coarsen=None,
-                    res_path=None, pack=None):
-        """One frame of the batch decode on the calling frame thread: .bin -> x_hat (or its subset: canonical channels /
-        box / step / coarsen of VAEformer._subset_args / _step_arg / _coarsen_arg) -> this thread's pinned buffer -> `sink` / `out[i]` / a fresh
-        array.  pack (_pack_arg): the frame is packed to int16 on this thread's stream first and the codes cross instead."""
-        lstrings, shape = self._read_bin(path)
-        side = self._residual_load(res_path) if res_path is not None else None
+    def _read_frame(self, path, res_path=None):
+        """-> (strings, z shape) of the .bin at `path` and the sidecar of `res_path` on the device (None without one)."""
+        strings, shape = self._read_bin(path)
+        return strings, shape, self._residual_load(res_path) if res_path is not None else None
+
+    def _decode_device(self, strings, shape, denorm, sel, side=None, what=None, phase="decompress"):
+        """One frame's strings -> the selection `sel` of its reconstruction on the device, contiguous [C', Hb, Wb], de-
+        normalised in the overlap-add store with `denorm`; logged as `phase` (None: the caller's own phase covers it).
+        side (_residual_load): the sidecar's corrections are then added in place (_residual_correct; `what` names the
+        frame in its errors), logged as "residual"."""
+        t_d = time.perf_counter()
+        x_hat = self.net._decompress_frame(strings[0][0], strings[1][0], shape, True,
+                                           mean=self._mean_flat if denorm else None,
+                                           std=self._std_flat if denorm else None, **sel.model)
+        if phase is not None:
+            self._log(phase, t_d)
+        if side is not None:
+            self._residual_correct(x_hat, side, sel, what)
+        return x_hat.reshape(x_hat.shape[-3:])
+
+    def _decode_one(self, i, path, denorm, sel, out=None, sink=None, res_path=None, pack=None):
+        """One frame of the batch decode on the calling frame thread: .bin -> the Selection `sel` of x_hat -> this thread's
+        pinned buffer -> `sink` / `out[i]` / a fresh array.  pack (_pack_arg): the frame is packed to int16 on this
+        thread's stream first and the codes cross instead."""
+        strings, shape, side = self._read_frame(path, res_path)
         with torch.no_grad():
-            t_d = time.perf_counter()
-            x_hat = self.net._decompress_frame(lstrings[0][0], lstrings[1][0], shape, True,
-                                               mean=self._mean_flat if denorm else None,
-                                               std=self._std_flat if denorm else None, channels=channels, box=box,
-                                               step=step, coarsen=coarsen)
-            self._log("decompress", t_d)
-            if side is not None:
-                self._residual_correct(x_hat, side, channels, box, step, res_path)
-            C, H, W = x_hat.shape[-3:]
-            if pack is not None:
-                return self._decode_one_packed(i, x_hat.reshape(C, H, W), pack, out, sink)
-            pin = self.net._pinned("api_x_out", (C, H, W), torch.float32)
+            return self._frame_out(i, self._decode_device(strings, shape, denorm, sel, side, res_path), pack, out, sink)
+
+    def _frame_out(self, i, x, pk, out, sink):
+        """_decode_one's way out: x [C', H, W] on the device -> this thread's pinned buffer in ONE turn on the link ->
+        `sink(i, .)` / `out[i]` / a fresh copy.  With pk (pack=) the codes and the table cross instead (half the bytes of
+        the fp32 frame) and the item is the dict of pack.pack_frame, q the host array."""
+        shape = tuple(x.shape)
+        if pk is None:
+            pin = self.net._pinned("api_x_out", shape, torch.float32)
             if sink is None and out is not None and self.batch_copy_threads > 1:
                 with self._link("d2h"):
-                    ops.copy_d2h_staged(out[i], x_hat.reshape(C, H, W), pin, threads=self.batch_copy_threads)
+                    ops.copy_d2h_staged(out[i], x, pin, threads=self.batch_copy_threads)
                 return out[i]
-            with self._link("d2h"):
-                pin.copy_(x_hat, non_blocking=True)
-                torch.cuda.current_stream().synchronize()
+            crossing = [(pin, x)]
+        else:
+            q, table, fixed = self._pack_device(x, pk, q_out=self.net._buf("api_q_dev", shape, torch.int16),
+                                                table_out=self.net._buf("api_pack_table", (shape[0], len(ops.PACK_FIELDS)),
+                                                                        torch.float64))
+            pin = self.net._pinned("api_q_out", shape, torch.int16)
+            tpin = self.net._pinned("api_pack_table_out", tuple(table.shape), torch.float64)
+            crossing = [(pin, q), (tpin, table)]
+        with self._link("d2h"):
+            for host, dev in crossing:
+                host.copy_(dev, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
         t_s = time.perf_counter()
         try:
+            def item(frame):
+                return frame if pk is None else dict(_pk.frame_stats(tpin.numpy(), fixed), q=frame)
             if sink is not None:
-                return sink(i, pin.numpy())
+                return sink(i, item(pin.numpy()))
             if out is not None:
                 np.copyto(out[i], pin.numpy())
-                return out[i]
-            return pin.numpy().copy()
+                return item(out[i])
+            return item(pin.numpy().copy())
         finally:
             self._log("consume", t_s)
 
-    def _pack_arg(self, what, pack, return_format, meta, per_variable=False):
+    def _pack_arg(self, what, pack, return_format, sel, per_variable=False):
         """pack= of the decode methods -> None, or dict(fixed: float64 numpy [C', 2] (pack.resolve_ranges over the decoded
         channels' names), fixed_dev: the same on the device | None when no range is fixed, groups: None - or, with
         per_variable, the channel rows of every pressure variable with more than one decoded level: they share one range)."""
@@ -572,8 +613,7 @@ class cra5_api:
         if return_format not in ('de_normalized', 'de_normlized'):
             raise ValueError(f"{what}: pack= packs the de-normalised reconstruction (the ranges are in physical units); "
                              f"return_format={return_format!r} is not supported with it")
-        names = meta["variables"] if meta is not None else \
-            [self.channels_to_vname.get(c, str(c)) for c in range(self.net.cfg['out_chans'])]
+        names = sel.names
         fixed = _pk.resolve_ranges(pack, names)
         groups = None
         if per_variable:
@@ -603,44 +643,14 @@ class cra5_api:
             table = ops.pack_range(x, torch.from_numpy(fixed).to(x.device), out=table)
         return ops.pack_i16(x, table, out=q_out), table, fixed
 
-    def _decode_one_packed(self, i, x, pk, out, sink):
-        """_decode_one's way out with pack=: x [C', H, W] on the device -> codes and table through this thread's pinned
-        buffers in ONE turn on the link (half the bytes of the fp32 frame) -> the dict of pack.pack_frame, q a host array."""
-        shape = tuple(x.shape)
-        q, table, fixed = self._pack_device(x, pk, q_out=self.net._buf("api_q_dev", shape, torch.int16),
-                                            table_out=self.net._buf("api_pack_table", (shape[0], len(ops.PACK_FIELDS)),
-                                                                    torch.float64))
-        pin = self.net._pinned("api_q_out", shape, torch.int16)
-        tpin = self.net._pinned("api_pack_table_out", tuple(table.shape), torch.float64)
-        with self._link("d2h"):
-            pin.copy_(q, non_blocking=True)
-            tpin.copy_(table, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-        t_s = time.perf_counter()
-        try:
-            item = _pk.frame_stats(tpin.numpy(), fixed)
-            if sink is not None:
-                item["q"] = pin.numpy()
-                return sink(i, item)
-            if out is not None:
-                np.copyto(out[i], pin.numpy())
-                item["q"] = out[i]
-            else:
-                item["q"] = pin.numpy().copy()
-            return item
-        finally:
-            self._log("consume", t_s)
-
-    def _check_out(self, out, n, frame_shape=None, dtype=np.float32):
+    @staticmethod
+    def _check_out(out, n, frame_shape, dtype=np.float32):
         """`out=` of the batch methods: the C memcpy / DMA behind it writes n x C x H x W values of `dtype` (float32; int16
-        with pack=) (`frame_shape` = (C, H, W): a subset's), so anything else is refused here with a ValueError (not an
-        assert that `python -O` drops - ADVICE r5)."""
+        with pack=) (`frame_shape` = (C, H, W): the Selection's), so anything else is refused here with a ValueError (not
+        an assert that `python -O` drops - ADVICE r5)."""
         if out is None:
             return
-        C = self.net.cfg['out_chans']
-        H, W = self.net.cfg['img_size']
-        if frame_shape is not None:
-            C, H, W = frame_shape
+        C, H, W = frame_shape
         if not isinstance(out, np.ndarray) or out.dtype != dtype or tuple(out.shape) != (n, C, H, W) \
                 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
             raise ValueError(f"`out` must be a writeable C-contiguous {np.dtype(dtype).name} numpy array of shape [{n}, {C}, {H}, {W}]"
@@ -653,17 +663,16 @@ class cra5_api:
         `sink(i, frame)` / `out[i]`, `workers` frames in flight - the H2D of one frame, the D2H of another and the GPU /
         rANS phases of the rest overlap.  Returns [(encode dict, sink's value | host array), ...]."""
         save_root = save_root or self.local_root
-        if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
-            raise ValueError(f"unknown return_format {return_format!r}")
-        denorm = return_format != 'normalized'
+        denorm = self._denorm_arg(return_format)
         self.net._require_gpu()
-        self._check_out(out, len(time_stamps))
+        sel = self._select()
+        self._check_out(out, len(time_stamps), sel.shape)
         frames = list(data) if data is not None else [None] * len(time_stamps)
 
         def one(item):
             i, ts, arr = item
             enc = self._encode_one(ts, arr, save_root, True)
-            return enc, self._decode_one(i, enc["save_path"], denorm, out, sink)
+            return enc, self._decode_one(i, enc["save_path"], denorm, sel, out, sink)
         return self._pipeline(workers).map(one, [(i, ts, a) for i, (ts, a) in enumerate(zip(time_stamps, frames))])
 
     def decode_batch(self, time_stamps=None, paths=None, return_format='de_normalized', out=None, workers=12, sink=None,
@@ -694,21 +703,16 @@ class cra5_api:
     def _decode_batch(self, time_stamps, paths, return_format, out, workers, sink, variables, region, stride, coarsen,
                       residual, pack, what="decode_batch", per_variable=False):
         if paths is None:
-            paths = [f'{self.local_root}/CRA5/{ts[:4]}/{ts}.bin' for ts in time_stamps]
-        if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
-            raise ValueError(f"unknown return_format {return_format!r}")
-        denorm = return_format != 'normalized'
+            paths = [self._bin_path(ts) for ts in time_stamps]
+        denorm = self._denorm_arg(return_format)
         self.net._require_gpu()
-        channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
-        sides = self._residual_arg(what, residual, list(paths), return_format, sel["coarsen"])
-        pk = self._pack_arg(what, pack, return_format, meta, per_variable)
-        shape = None
-        if meta is not None:
-            shape = (len(meta["variables"]), len(meta["lat"]), len(meta["lon"]))
-        self._check_out(out, len(paths), shape, np.int16 if pk is not None else np.float32)
+        sel = self._select(variables, region, stride, coarsen)
+        sides = self._residual_arg(what, residual, list(paths), return_format, sel.coarsen)
+        pk = self._pack_arg(what, pack, return_format, sel, per_variable)
+        self._check_out(out, len(paths), sel.shape, np.int16 if pk is not None else np.float32)
 
-        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, out, sink, channels, box,
-                                                                       res_path=sides[it[0]], pack=pk, **sel),
+        return self._pipeline(workers).map(lambda it: self._decode_one(it[0], it[1], denorm, sel, out, sink,
+                                                                       res_path=sides[it[0]], pack=pk),
                                            list(enumerate(paths)))
 
     def decode_to_nc(self, time_stamps=None, paths=None, save_root=None, pack="int16", variables=None, region=None,
@@ -733,26 +737,20 @@ class cra5_api:
         if paths is not None and len(list(paths)) != len(time_stamps):
             raise ValueError("decode_to_nc: time_stamps and paths must have the same length")
         save_root = save_root or self.local_root
-        _, _, _, meta = self._subset(variables, region, stride, coarsen)
-        if meta is None:
-            H, W = self.net.cfg['img_size']
-            g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W)
-            meta = dict(variables=[self.channels_to_vname.get(c, str(c)) for c in range(self.net.cfg['out_chans'])],
-                        lat=g["lat"], lon=g["lon"])
-        names, lat, lon = meta["variables"], meta["lat"], meta["lon"]
+        sel = self._select(variables, region, stride, coarsen)
 
         def sink(i, item):
             t0 = time.perf_counter()
-            files = _pk.write_era5_nc(save_root, time_stamps[i], item, names, lat, lon, self.vnames)
+            files = _pk.write_era5_nc(save_root, time_stamps[i], item, sel.names, sel.lat, sel.lon, self.vnames)
             self._log("write_nc", t0)
             return dict(time_stamp=time_stamps[i], files=files, bytes=sum(os.path.getsize(p) for p in files))
         return self._decode_batch(time_stamps, paths, 'de_normalized', None, workers, sink, variables, region, stride,
                                   coarsen, residual, pack, what="decode_to_nc", per_variable=True)
 
-    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, coarsen=None, spectrum=False, tol=None):
+    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, sel, spectrum=False, tol=None):
         """One frame of evaluate_batch on the calling frame thread: the truth is staged once into this thread's device
         frame buffer; the reconstruction comes from the in-memory strings (bin_path None) or from `bin_path`, and only
-        the per-channel statistics leave the device.  coarsen = (k_lat, k_lon): both frames are coarsened on the device
+        the per-channel statistics leave the device.  sel.coarsen = (k_lat, k_lon): both frames are coarsened on the device
         by the same kernel (the reconstruction inside its decode, the truth by VAEformer.coarsen_frame) and compared on
         the coarse grid.  spectrum: the zonal power spectra of the same device pair join the report."""
         from . import metrics
@@ -770,41 +768,35 @@ class cra5_api:
             with torch.no_grad():
                 x = self._stage_in(arr)      # (a truth with masked / non-finite values is reported, not refused)
         with torch.no_grad():
-            t_d = time.perf_counter()
-            x_hat = self.net._decompress_frame(strings[0][0], strings[1][0], shape, True,
-                                               mean=self._mean_flat, std=self._std_flat, coarsen=coarsen)
-            self._log("decompress", t_d)
+            x_hat = self._decode_device(strings, shape, True, sel)
             side = None
             if tol is not None:
                 # the reconstruction a decode with the sidecar would see: quantise against the staged truth, correct in place
                 t_r = time.perf_counter()
                 side = self._residual_build(ts, x, x_hat, tol, None)
-                grid = tuple(x_hat.shape[-3:])
-                ops.residual_apply(x_hat.reshape(grid), side["records"], side["step"], grid)
+                ops.residual_apply(x_hat, side["records"], side["step"], tuple(x_hat.shape))
                 if bin_path is None and save_root is not None:
                     self._residual_write(side, enc["save_path"])
                 self._log("residual", t_r)
             t_m = time.perf_counter()
             C, H, W = x.shape[-3:]
             x = x.reshape(C, H, W)
-            if coarsen is not None:
+            if sel.coarsen is not None:
                 if (C, H, W) != (self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size']):
                     raise ValueError(f"{ts}: the truth frame is {(C, H, W)}, the model's grid "
                                      f"{(self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size'])}")
-                Ho, Wo = self.net._decoded_shape(None, None, coarsen=coarsen)[-2:]
                 # this thread's persistent workspace, like the decode's own buffers: no allocation per frame
-                x = self.net.coarsen_frame(x.contiguous(), coarsen, out=self.net._buf("eval_truth_coarse", (C, Ho, Wo)))
-            Ce, He, We = x.shape
-            if tuple(x_hat.shape[-3:]) != (Ce, He, We):
-                raise ValueError(f"{ts}: the reconstruction is {tuple(x_hat.shape[-3:])}, the truth frame {(Ce, He, We)}")
-            err = metrics.reconstruction_error(x_hat.reshape(Ce, He, We), x, lat_weights=lat_weights)
+                x = self.net.coarsen_frame(x.contiguous(), sel.coarsen, out=self.net._buf("eval_truth_coarse", sel.shape))
+            if x_hat.shape != x.shape:
+                raise ValueError(f"{ts}: the reconstruction is {tuple(x_hat.shape)}, the truth frame {tuple(x.shape)}")
+            err = metrics.reconstruction_error(x_hat, x, lat_weights=lat_weights)
             self._log("metrics", t_m)
             if spectrum:
                 t_s = time.perf_counter()
-                spec = metrics.zonal_spectrum(x_hat.reshape(Ce, He, We), x, lat_weights=lat_weights)
+                spec = metrics.zonal_spectrum(x_hat, x, lat_weights=lat_weights)
                 self._log("spectrum", t_s)
         std = self._std_flat.detach().cpu().numpy().astype(np.float64)
-        rep = dict(time_stamp=ts, variables=[self.channels_to_vname.get(c, str(c)) for c in range(C)])
+        rep = dict(time_stamp=ts, variables=list(sel.names))
         rep.update(err)
         rep["rmse_norm"] = err["rmse"] / std
         if spectrum:
@@ -844,18 +836,15 @@ class cra5_api:
         (bin_bytes + res_bytes); compression_ratio stays that of the .bin.  No budget applies here.  With save_root (and
         bins=None) the .res is written beside the .bin."""
         self.net._require_gpu()
-        H, W = self.net.cfg['img_size']
-        k = self.net._coarsen_arg(coarsen, None)
+        sel = self._select(coarsen=coarsen)
+        k = sel.coarsen
         tol = self._residual_tol(max_error)
         if tol is not None and k is not None:
             raise ValueError("evaluate_batch: max_error with coarsen= is not supported - the correction belongs before the "
                              "averaging, on the full grid; evaluate the two separately")
-        extra = {}
-        if k is not None:
-            g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W, coarsen=k)
-            extra = dict(coarsen=k, lat=g["lat"], lon=g["lon"])
+        extra = dict(coarsen=k, lat=sel.lat, lon=sel.lon) if k is not None else {}
         if spectrum:
-            Wc = W if k is None else self.net._decoded_shape(None, None, coarsen=k)[-1]
+            Wc = sel.shape[-1]
             if not ops.spectrum_width_ok(Wc):
                 raise ValueError(f"evaluate_batch(spectrum=True): the compared width {Wc} is not supported - the row "
                                  f"transform takes 2 <= W <= {ops.SPECTRUM_MAX_W} with no prime factor above 5")
@@ -864,31 +853,23 @@ class cra5_api:
         if len(frames) != n or (bins is not None and len(bins) != n):
             raise ValueError("evaluate_batch: time_stamps, data and bins must have the same length")
         paths = list(bins) if bins is not None else [None] * n
-        reps = self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights, k,
+        reps = self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights, sel,
                                                                          bool(spectrum), tol),
                                            list(zip(time_stamps, frames, paths)))
         for r in reps:
             r.update(extra)
         return reps
 
-    def _aggregate_one(self, path, denorm, channels, box, sel, frame_shape, acc, seq, res_path=None):
+    def _aggregate_one(self, path, denorm, sel, acc, seq, res_path=None):
         """One frame of aggregate_batch on the calling frame thread: .bin -> x_hat (or its subset) -> folded into the
         group's device accumulators as turn `seq`, on this frame's stream.  Nothing crosses to the host."""
-        lstrings, shape = self._read_bin(path)
-        side = self._residual_load(res_path) if res_path is not None else None
+        strings, shape, side = self._read_frame(path, res_path)
         with torch.no_grad():
-            t_d = time.perf_counter()
-            x_hat = self.net._decompress_frame(lstrings[0][0], lstrings[1][0], shape, True,
-                                               mean=self._mean_flat if denorm else None,
-                                               std=self._std_flat if denorm else None, channels=channels, box=box,
-                                               **sel)
-            self._log("decompress", t_d)
-            if side is not None:
-                self._residual_correct(x_hat, side, channels, box, sel["step"], res_path)
+            x_hat = self._decode_device(strings, shape, denorm, sel, side, res_path)
             t_a = time.perf_counter()
-            if tuple(x_hat.shape[-3:]) != frame_shape or x_hat.numel() != frame_shape[0] * frame_shape[1] * frame_shape[2]:
-                raise ValueError(f"{path}: the reconstruction is {tuple(x_hat.shape)}, the accumulators {frame_shape}")
-            acc.add(x_hat.reshape(frame_shape), seq=seq)
+            if tuple(x_hat.shape) != sel.shape:
+                raise ValueError(f"{path}: the reconstruction is {tuple(x_hat.shape)}, the accumulators {sel.shape}")
+            acc.add(x_hat, seq=seq)
             self._log("accumulate", t_a)
 
     def aggregate_batch(self, time_stamps=None, paths=None, stats=("mean", "std", "min", "max"), groups=None, ddof=0,
@@ -917,7 +898,7 @@ class cra5_api:
         if paths is None:
             if time_stamps is None:
                 raise ValueError("aggregate_batch needs time_stamps or paths")
-            paths = [f'{self.local_root}/CRA5/{ts[:4]}/{ts}.bin' for ts in time_stamps]
+            paths = [self._bin_path(ts) for ts in time_stamps]
         paths = list(paths)
         if not paths:
             raise ValueError("aggregate_batch: no frame given")
@@ -925,9 +906,7 @@ class cra5_api:
         if return_format == 'latent':
             raise ValueError("aggregate_batch: return_format='latent' is the latent, not a reconstruction to reduce; "
                              "use 'de_normalized' or 'normalized'")
-        if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
-            raise ValueError(f"unknown return_format {return_format!r}")
-        denorm = return_format != 'normalized'
+        denorm = self._denorm_arg(return_format)
         if groups is None:
             labels, member = [None], [0] * len(paths)
         else:
@@ -942,18 +921,12 @@ class cra5_api:
             g = counts.index(min(counts))
             raise ValueError(f"aggregate_batch: std with ddof = {ddof} needs more than {ddof} frame(s) per group; "
                              + (f"group {labels[g]!r} holds {counts[g]}" if groups is not None else f"{counts[g]} given"))
-        channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
-        sides = self._residual_arg("aggregate_batch", residual, paths, return_format, sel["coarsen"])
-        if meta is None:
-            H, W = self.net.cfg['img_size']
-            g = subset.grid_box((-90.0, 90.0, 0.0, 360.0), H, W)
-            meta = dict(variables=[self.channels_to_vname.get(c, str(c)) for c in range(self.net.cfg['out_chans'])],
-                        lat=g["lat"], lon=g["lon"])
-        frame_shape = (len(meta["variables"]), len(meta["lat"]), len(meta["lon"]))
+        sel = self._select(variables, region, stride, coarsen)
+        sides = self._residual_arg("aggregate_batch", residual, paths, return_format, sel.coarsen)
         self.net._require_gpu()
 
         # every accumulator before the first decode: running out of device memory shows here
-        accs = [TimeStats(frame_shape, stats=stats, device=self.net.device, ddof=ddof) for _ in labels]
+        accs = [TimeStats(sel.shape, stats=stats, device=self.net.device, ddof=ddof) for _ in labels]
         seqs, seen = [], [0] * len(labels)
         for g in member:
             seqs.append(seen[g])
@@ -961,14 +934,14 @@ class cra5_api:
 
         def one(i):
             try:
-                self._aggregate_one(paths[i], denorm, channels, box, sel, frame_shape, accs[member[i]], seqs[i], sides[i])
+                self._aggregate_one(paths[i], denorm, sel, accs[member[i]], seqs[i], sides[i])
             except BaseException as e:
                 for a in accs:       # nobody waits for this frame's turn, and the call ends with this frame's error
                     a.abort(e)
                 raise
         self._pipeline(workers).map(one, list(range(len(paths))))
 
-        res = dict(meta)
+        res = sel.meta
         done = [a.result() for a in accs]
         if groups is not None:
             res["groups"] = labels
@@ -980,9 +953,9 @@ class cra5_api:
                 res[s] = torch.stack([d[s] for d in done]) if groups is not None else done[0][s]
             return res
         t0 = time.perf_counter()
-        pin = self.net._pinned("api_x_out", frame_shape, torch.float32)
+        pin = self.net._pinned("api_x_out", sel.shape, torch.float32)
         for s in stats:
-            host = np.empty(((len(labels),) if groups is not None else ()) + frame_shape, dtype=np.float32)
+            host = np.empty(((len(labels),) if groups is not None else ()) + sel.shape, dtype=np.float32)
             for g, d in enumerate(done):
                 ops.copy_d2h_staged(host[g] if groups is not None else host, d[s], pin, threads=self.runtime.copy_threads)
             res[s] = host
@@ -1010,8 +983,7 @@ class cra5_api:
         widx = _res.witness_indices(C, H, W)
         got = ops.residual_gather(x_hat, torch.from_numpy(widx.view(np.int32)).to(dev), (C, H, W))
         idx, q, eidx, ebits, per = ops.residual_quantize(x, x_hat, tol)
-        names = [self.channels_to_vname.get(c, str(c)) for c in range(C)]
-        _res.check_budget(per, tol, H * W, max_fraction, names)
+        _res.check_budget(per, tol, H * W, max_fraction, self._names())
         parts, off = [], 0
         for t in (got.reshape(-1), idx, q, eidx, ebits):
             parts.append((off, t))
@@ -1031,12 +1003,12 @@ class cra5_api:
         return dict(blob=blob, records=(idx, q, eidx, ebits), step=torch.from_numpy(np.float32(2) * tol).to(dev),
                     records_n=int(per[:, 0].sum()), escapes_n=int(per[:, 1].sum()), per_channel=per, tol=tol)
 
-    def _residual_encode(self, ts, x, y_str, z_str, shape, tol, max_fraction):
+    def _residual_encode(self, ts, x, output, tol, max_fraction):
         """The encoder's side of the residual layer for one frame: decode the frame's own strings (the whole frame,
         de-normalised: the x_hat every decoder of this .bin computes, bit for bit) and quantise the staged truth against
         it."""
         t_r = time.perf_counter()
-        x_hat = self.net._decompress_frame(y_str, z_str, shape, True, mean=self._mean_flat, std=self._std_flat)
+        x_hat = self._decode_device(output["strings"], output["z_shape"], True, self._select(), phase=None)
         side = self._residual_build(ts, x, x_hat, tol, max_fraction)
         self._log("residual", t_r)
         return side
@@ -1098,14 +1070,15 @@ class cra5_api:
         side["grid"] = grid
         return side
 
-    def _residual_correct(self, x_hat, side, channels, box, step, what):
-        """Correct the decode's device output IN PLACE (x_hat [.., C', Ho, Wo]: canonical channels / box / step of
-        _subset_args / _step_arg).  The sidecar's witnesses inside the subset are compared with the plain decode first:
+    def _residual_correct(self, x_hat, side, sel, what):
+        """Correct the decode's device output IN PLACE (x_hat [.., C', Ho, Wo]: the Selection `sel` of the frame).  The
+        sidecar's witnesses inside the subset are compared with the plain decode first:
         ResidualMismatchError before anything is written."""
         out = x_hat.reshape(x_hat.shape[-3:])
         if out.data_ptr() != x_hat.data_ptr():
             raise RuntimeError("residual: the decode's output is not contiguous")
         lut = None
+        channels, box, step = sel.channels, sel.box, sel.step
         if channels is not None:
             lut = np.full(side["C"], -1, dtype=np.int32)
             lut[list(channels)] = np.arange(len(channels), dtype=np.int32)
@@ -1117,6 +1090,17 @@ class cra5_api:
         self._log("residual", t_r)
 
     # ------------------------------------------------------------------ decode
+    def _bin_path(self, ts):
+        """The default archive path of time stamp `ts`."""
+        return f'{self.local_root}/CRA5/{ts[:4]}/{ts}.bin'
+
+    @staticmethod
+    def _denorm_arg(return_format):
+        """return_format of a reconstruction -> whether it is de-normalised; ValueError for an unknown one."""
+        if return_format not in ('de_normalized', 'de_normlized', 'normalized'):
+            raise ValueError(f"unknown return_format {return_format!r}")
+        return return_format != 'normalized'
+
     def _read_bin(self, bin_path):
         with Path(bin_path).open("rb") as f:
             return binfmt.unpack_bin(f.read())
@@ -1127,16 +1111,15 @@ class cra5_api:
         if bin_path is None:
             if time_stamp is None:
                 raise ValueError("bin_to_latent needs bin_path or time_stamp")
-            bin_path = f'{self.local_root}/CRA5/{time_stamp[:4]}/{time_stamp}.bin'
+            bin_path = self._bin_path(time_stamp)
         lstrings, shape = self._read_bin(bin_path)
         with torch.no_grad():
             return self.net.decompress(lstrings, shape, return_format='latent')
 
     def latent_to_reconstruction(self, y_hat, variables=None, region=None, stride=None, coarsen=None):
         """cra5_api.py:146-151 (normalised units).  variables / region / stride / coarsen: that subset (decode_from_bin)."""
-        channels, box, sel, _ = self._subset(variables, region, stride, coarsen)
         with torch.no_grad():
-            return self.net.decode_latent(y_hat, channels=channels, box=box, **sel)
+            return self.net.decode_latent(y_hat, **self._select(variables, region, stride, coarsen).model)
 
     def decode_from_bin(self, time_stamp=None, custom_path=None, return_format='de_normalized', to_host=False, out=None,
                         variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None):
@@ -1179,29 +1162,27 @@ class cra5_api:
                                           or coarsen is not None):
             raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region / stride / "
                              "coarsen select a subset of the reconstruction")
-        if return_format not in ('latent', 'normalized', 'de_normalized', 'de_normlized'):
-            raise ValueError(f"unknown return_format {return_format!r}")
-        channels, box, sel, meta = self._subset(variables, region, stride, coarsen)
-        bin_path = custom_path or f'{self.local_root}/CRA5/{time_stamp[:4]}/{time_stamp}.bin'
+        if return_format != 'latent':
+            self._denorm_arg(return_format)
+        sel = self._select(variables, region, stride, coarsen)
+        bin_path = custom_path or self._bin_path(time_stamp)
         res_path = self._residual_arg("decode_from_bin", residual if residual is None or isinstance(residual, bool) else [residual],
-                                      [bin_path], return_format, sel["coarsen"])[0]
-        pk = self._pack_arg("decode_from_bin", pack, return_format, meta)
+                                      [bin_path], return_format, sel.coarsen)[0]
+        pk = self._pack_arg("decode_from_bin", pack, return_format, sel)
         stats = None
         decoding_start = time.time()
-        lstrings, shape = self._read_bin(bin_path)
-        side = self._residual_load(res_path) if res_path is not None else None
+        lstrings, shape, side = self._read_frame(bin_path, res_path)
         with torch.no_grad():
             y_hat = self.net.decompress(lstrings, shape, return_format='latent')
             if return_format == 'latent':
                 return y_hat
             if return_format == 'normalized':
-                x_hat = self.net.decode_latent(y_hat, channels=channels, box=box, **sel)
+                x_hat = self.net.decode_latent(y_hat, **sel.model)
             else:
                 # fused de-normalisation in the overlap-add store
-                x_hat = self.net._decode_guarded(y_hat[0], mean=self._mean_flat, std=self._std_flat, channels=channels,
-                                                 box=box, **sel)
+                x_hat = self.net._decode_guarded(y_hat[0], mean=self._mean_flat, std=self._std_flat, **sel.model)
                 if side is not None:
-                    self._residual_correct(x_hat, side, channels, box, sel["step"], res_path)
+                    self._residual_correct(x_hat, side, sel, res_path)
             ht, dt = (np.float32, torch.float32) if pk is None else (np.int16, torch.int16)
             if pk is not None:
                 x_hat, table, fixed = self._pack_device(x_hat.reshape(x_hat.shape[-3:]), pk)
@@ -1216,8 +1197,8 @@ class cra5_api:
                 x_hat = ops.copy_d2h_staged(out, src, pin, threads=self.runtime.copy_threads)
         torch.cuda.synchronize()
         res = dict(x_hat=x_hat, decoding_time=time.time() - decoding_start)
-        if meta is not None:
-            res.update(meta)
+        if not sel.whole:
+            res.update(sel.meta)
         if stats is not None:
             res.update(stats)
         return res

@@ -863,6 +863,13 @@ class VAEformer(nn.Module):
             subset.kept_points(box if box is not None else (0, H, 0, W), k, W)
         return k
 
+    def _selection_args(self, channels=None, box=None, step=None, coarsen=None):
+        """-> the canonical (channels, box, step, coarsen) of _subset_args, _step_arg and _coarsen_arg, each validated
+        against the ones before it: what _decode_frame and everything below it take."""
+        channels, box = self._subset_args(channels, box)
+        step = self._step_arg(step, box)
+        return channels, box, step, self._coarsen_arg(coarsen, box, step)
+
     def _coarsen_tables(self, box, k):
         """(subset.coarsen_plan, ops.coarsen_tables) of the canonical box and factor - built once per (box, k), cached
         like the stride tables."""
@@ -1293,9 +1300,7 @@ class VAEformer(nn.Module):
         mean of the full decode over the coarse cell round each (first-order conservative; subset.coarsen_plan, DESIGN.md
         section 4): fixed float64 arithmetic, a region's result is the sub-block of the globe's bit for bit."""
         self._require_gpu()
-        channels, box = self._subset_args(channels, box)
-        step = self._step_arg(step, box)
-        coarsen = self._coarsen_arg(coarsen, box, step)
+        channels, box, step, coarsen = self._selection_args(channels, box, step, coarsen)
         # the batch result is allocated once and every frame's un-embed stores into its slice (no stack copy)
         out = torch.empty((y.shape[0],) + self._decoded_shape(channels, box, step, coarsen), device=self.device,
                           dtype=torch.float32)
@@ -1531,9 +1536,7 @@ class VAEformer(nn.Module):
         if not rec and (channels is not None or box is not None or step is not None or coarsen is not None):
             raise ValueError("decompress: return_format='latent' returns the latent; channels / box / step / coarsen "
                              "select a subset of the reconstruction")
-        channels, box = self._subset_args(channels, box)
-        step = self._step_arg(step, box)
-        coarsen = self._coarsen_arg(coarsen, box, step)
+        channels, box, step, coarsen = self._selection_args(channels, box, step, coarsen)
         self.entropy_bottleneck._check()
         self.gaussian_conditional._check()
         B = len(strings[0])

@@ -1,13 +1,14 @@
 """Subset decode, host side (no GPU): the lat/lon box -> grid rows / columns rules (cra5_api.grid_box), variable names ->
-channel indices for the 268- and a 159-variable configuration, the token range of the un-embed superset, and the C ABI's
-argument validation of the two new kernels."""
+channel indices for the 268- and a 159-variable configuration, the token range of the un-embed superset, the C ABI's
+argument validation of the two new kernels, and the Selection record cra5_api._select makes of the decode arguments."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from cra5_amd import _lib, subset
+from cra5_amd import _lib, subset, synth
 from cra5_amd.api import cra5_api, variable_mapping
+from cra5_amd.vaeformer import VAEformer
 
 H, W = 721, 1440
 ERR_ARG = -7
@@ -177,3 +178,85 @@ def test_new_kernels_validate_arguments_without_gpu():
     # CRA5_GEMM_WIDE_K exists with CRA5_GEMM_HI_ONLY only
     assert L.cra5_gemm_nt_split(fake_a, 64, fake_b, 64, fake_b, 64, None, 0, None, None, 0, 1, 1, 64, 1.0, 128,
                                 None) == ERR_ARG
+
+
+# ---- the Selection record of the decode methods ------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module")
+def thin_api():
+    return cra5_api(device="cpu", weights=VAEformer(0, **synth.thin_model_kwargs()))
+
+
+GLOBE = (-90, 90, 0, 360)
+ALL_8 = ["z_1000", "z_975", "z_950", "z_925", "z_900", "z_875", "z_850", "z_825"]     # the thin model's channels, in order
+# (variables, region, stride, coarsen), every argument canonical-None, whole
+SELECTIONS = [
+    (None, None, None, None, True, True),
+    (["z_850", "z_1000", "z_925"], None, None, None, False, False),       # not sorted: the order given
+    (None, (35, 72, 0, 10), None, None, False, False),
+    (None, (-10.3, 20.1, 350.2, 9.9), None, None, False, False),          # across 0 deg: the columns wrap at W
+    (None, (-60, 60, 170, -170), None, None, False, False),               # across the date line
+    (None, None, 6, None, False, False),
+    (None, (35, 72, -25, 45), (6, 4), None, False, False),
+    (None, None, None, 6, False, False),
+    (["z_825", "z_975"], (-30, 30, 350, 20), None, (6, 4), False, False),
+    # the no-op spellings: the model takes the whole-frame path for each of them
+    (None, None, 1, None, True, True),
+    (None, None, None, (1, 1), True, True),
+    # ... and these two name a region / variables: decode_from_bin's dict carries variables, lat and lon for them
+    (None, GLOBE, None, None, True, False),
+    (ALL_8, None, None, None, True, False),
+]
+
+
+@pytest.mark.parametrize("variables, region, stride, coarsen, noop, whole", SELECTIONS)
+def test_select_record(thin_api, variables, region, stride, coarsen, noop, whole):
+    """_select against the pieces composed by hand: subset.resolve_variables and subset.grid_box for the request, the
+    model's _subset_args / _step_arg / _coarsen_arg for the canonical arguments, _decoded_shape for the frame."""
+    api, net = thin_api, thin_api.net
+    sel = api._select(variables, region, stride, coarsen)
+    chans = subset.resolve_variables(variables, api.vname_to_channels)
+    g = subset.grid_box(region if region is not None else GLOBE, H, W, stride=stride, coarsen=coarsen)
+    channels, box = net._subset_args(chans, g["box"] if region is not None else None)
+    step = net._step_arg(stride, box)
+    k = net._coarsen_arg(coarsen, box, step)
+    assert (sel.channels, sel.box, sel.step, sel.coarsen) == (channels, box, step, k)
+    assert sel.model == dict(channels=channels, box=box, step=step, coarsen=k)
+    assert ((channels, box, step, k) == (None, None, None, None)) == noop
+    assert sel.shape == net._decoded_shape(channels, box, step, k)
+    assert sel.names == (list(variables) if variables is not None else ALL_8)
+    assert sel.lat.dtype == sel.lon.dtype == np.float64
+    assert np.array_equal(sel.lat, g["lat"]) and np.array_equal(sel.lon, g["lon"])
+    assert sel.shape == (len(sel.names), len(g["lat"]), len(g["lon"]))
+    meta = sel.meta
+    if k is None:
+        assert sel.lat_bnds is None and sel.lon_bnds is None
+        assert list(meta) == ["variables", "lat", "lon"]
+    else:
+        assert np.array_equal(sel.lat_bnds, g["lat_bnds"]) and np.array_equal(sel.lon_bnds, g["lon_bnds"])
+        assert sel.lat_bnds.shape == (sel.shape[1], 2) and sel.lon_bnds.shape == (sel.shape[2], 2)
+        assert list(meta) == ["variables", "lat", "lon", "coarsen", "lat_bnds", "lon_bnds"]
+        assert meta["coarsen"] == k and meta["lat_bnds"] is sel.lat_bnds and meta["lon_bnds"] is sel.lon_bnds
+    assert meta["variables"] is sel.names and meta["lat"] is sel.lat and meta["lon"] is sel.lon
+    assert sel.whole is whole
+    if whole:
+        assert sel.shape == (8, H, W) and sel.lat[0] == 90.0 and sel.lat[-1] == -90.0 and sel.lon[-1] == 359.75
+
+
+@pytest.mark.parametrize("kw, msg", [
+    (dict(stride=6, coarsen=6), "pass one of the two"),
+    (dict(stride=(1, 2), coarsen=(6, 1)), "pass one of the two"),
+    (dict(stride=7), r"1440 % s_lon \(7\)"),
+    (dict(coarsen=7), r"\(721 - 1\) % k_lat \(7\)"),
+    (dict(variables=["z_850", "z_501"]), r"unknown.*'z_501'"),
+    (dict(variables=["t2m"]), r"indices \[263\] outside \[0, 8\)"),            # a name of the 268 set the thin model lacks
+    (dict(variables=[]), "empty"),
+    (dict(region=(9.25, 10.25, 0, 10), stride=6), "hold no row"),               # rows 319 .. 323: none with row % 6 == 0
+    (dict(region=(0, 10, 0.25, 1), stride=6), "hold no column"),
+    (dict(region=(9.25, 10.25, 0, 10), coarsen=6), "hold no row"),
+    (dict(region=(20, 10, 0, 10)), "lat_min > lat_max"),
+])
+def test_select_refusals(thin_api, kw, msg):
+    with pytest.raises(ValueError, match=msg):
+        thin_api._select(**kw)
