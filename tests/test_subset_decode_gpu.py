@@ -112,6 +112,14 @@ BOXES = [
     (200, 260, 1, 1440),     # the full circle off a patch boundary
     (0, 721, 720, 1440),     # the whole globe centred on Greenwich
     (0, 721, 0, 1440),       # the whole globe
+    # supersets that take the LDS-tiled col2im (n_tj % 16 == 0) or sit on a 256-row tile edge of the un-embed launch
+    # (tests/patch_geometry_helpers.py MODEL_BOXES; tests/test_patch_geometry_inputs_cpu.py asserts each superset)
+    (205, 236, 403, 150),    # 4 x 16 tokens, away from the east edge
+    (301, 322, 1385, 155),   # 3 x 16 across the east edge
+    (401, 560, 800, 160),    # 16 x 16: M = 256, exactly one tile
+    (101, 130, 15, 850),     # 3 x 86: M = 258, the second tile holds two rows
+    (0, 15, 640, 320),       # 2 x 32 on the top edge
+    (700, 721, 1120, 160),   # 3 x 16 on the bottom edge
 ]
 ENGINES = {
     "default": {},
