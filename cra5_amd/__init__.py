@@ -22,6 +22,9 @@ def __getattr__(name):
     if name == "VAEformer":
         from .vaeformer import VAEformer
         return VAEformer
+    if name == "Grid":
+        from .regrid import Grid
+        return Grid
     raise AttributeError(name)
 
 

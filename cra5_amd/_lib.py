@@ -70,6 +70,8 @@ SIGNATURES = {
     "cra5_strided_scatter_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                          c_void_p, c_int, c_int, c_int, c_void_p]),
     "cra5_coarsen_f32": (c_int, [c_void_p] + [c_int] * 14 + [c_void_p] * 3 + [c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "cra5_regrid_f32": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 3 + [c_int] + [c_void_p] * 4 + [c_int, c_void_p] +
+                        [c_int] * 3 + [c_void_p, c_int, c_void_p, c_void_p]),
     "cra5_probe_sums_f32": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
     "cra5_recon_error_slab_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cra5_recon_error_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p,

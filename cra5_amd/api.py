@@ -94,18 +94,25 @@ class Selection(NamedTuple):
     lon_bnds: Optional[np.ndarray]
     shape: tuple                    # (C', Hb, Wb) of one decoded frame
     whole: bool                     # no argument asked for a subset: decode_from_bin's dict carries no extra keys
+    regrid: Optional[dict] = None   # the target grid's plan (VAEformer._regrid_arg); lat / lon / the bounds are then its
 
     @property
     def model(self):
-        """The keyword arguments of _decompress_frame / _decode_guarded / decode_latent."""
-        return dict(channels=self.channels, box=self.box, step=self.step, coarsen=self.coarsen)
+        """The keyword arguments of _decompress_frame / _decode_guarded / decode_latent (regrid only when asked for)."""
+        kw = dict(channels=self.channels, box=self.box, step=self.step, coarsen=self.coarsen)
+        if self.regrid is not None:
+            kw["regrid"] = self.regrid
+        return kw
 
     @property
     def meta(self):
-        """The result dicts' keys: variables, lat, lon - with coarsen also coarsen, lat_bnds, lon_bnds."""
+        """The result dicts' keys: variables, lat, lon - with coarsen also coarsen, lat_bnds, lon_bnds; with regrid also
+        regrid (the method), lat_bnds, lon_bnds."""
         meta = dict(variables=self.names, lat=self.lat, lon=self.lon)
         if self.coarsen is not None:
             meta.update(coarsen=self.coarsen, lat_bnds=self.lat_bnds, lon_bnds=self.lon_bnds)
+        if self.regrid is not None:
+            meta.update(regrid=self.regrid["method"], lat_bnds=self.lat_bnds, lon_bnds=self.lon_bnds)
         return meta
 
 
@@ -254,6 +261,10 @@ class cra5_api:
     # of the full decode over the coarse cell round each point - first-order conservative remapping, computed on the GPU
     # in fixed float64 arithmetic ("Coarsening"; (721 - 1) % k_lat == 0 and 1440 % k_lon == 0):
     # coarsen=6 is the conservative 1.5 deg field, 1 / 36 of the bytes.  The dict also carries coarsen, lat_bnds, lon_bnds.
+    # regrid=Grid(...) (cra5_amd.regrid; on its own - the target grid is the region and the resolution): the full decode on
+    # any rectilinear lat/lon grid, bilinear or first-order conservative, computed on the GPU in fixed float64 arithmetic
+    # from the source box the target needs ("Regridding"); only the target grid crosses the host
+    # link.  The dict also carries regrid (the method), lat_bnds, lon_bnds.
     grid_box = staticmethod(subset.grid_box)
     resolve_variables = staticmethod(subset.resolve_variables)
 
@@ -261,15 +272,26 @@ class cra5_api:
         """The names of the channels `chans`, in that order; None: of every channel of the model."""
         return [self.channels_to_vname.get(c, str(c)) for c in (chans if chans is not None else range(self.net.cfg['out_chans']))]
 
-    def _select(self, variables=None, region=None, stride=None, coarsen=None):
-        """The arguments of the decode methods -> their Selection; without any of them the whole grid's."""
+    def _select(self, variables=None, region=None, stride=None, coarsen=None, regrid=None):
+        """The arguments of the decode methods -> their Selection; without any of them the whole grid's.  regrid (a
+        regrid.Grid or its plan): the frame on that target grid - not together with region / stride / coarsen, the
+        target grid is the region and the resolution."""
         H, W = self.net.cfg['img_size']
         step, k = subset._stride_or_coarsen(stride, coarsen, H, W)
-        whole = variables is None and region is None and step is None and k is None
+        whole = variables is None and region is None and step is None and k is None and regrid is None
         chans = subset.resolve_variables(variables, self.vname_to_channels)
+        if regrid is not None:
+            for name, v in (("region", region), ("stride", step), ("coarsen", k)):
+                if v is not None:
+                    raise ValueError(f"regrid and {name} {v!r}: pass one of the two - the target grid is the region and "
+                                     f"the resolution")
+            names = self._names(chans)
+            channels, _, _, _, plan = self.net._selection_args(chans, None, None, None, regrid)
+            return Selection(channels, None, None, None, names, plan["lat"], plan["lon"], plan["lat_bnds"], plan["lon_bnds"],
+                             (len(names), plan["Ho"], plan["Wo"]), False, plan)
         g = subset.grid_box(region if region is not None else (-90.0, 90.0, 0.0, 360.0), H, W, stride=step, coarsen=k)
         names = self._names(chans)
-        channels, box, step, k = self.net._selection_args(chans, g["box"] if region is not None else None, step, k)
+        channels, box, step, k, _ = self.net._selection_args(chans, g["box"] if region is not None else None, step, k)
         return Selection(channels, box, step, k, names, g["lat"], g["lon"], g.get("lat_bnds"), g.get("lon_bnds"),
                          (len(names), len(g["lat"]), len(g["lon"])), whole)
 
@@ -676,7 +698,7 @@ class cra5_api:
         return self._pipeline(workers).map(one, [(i, ts, a) for i, (ts, a) in enumerate(zip(time_stamps, frames))])
 
     def decode_batch(self, time_stamps=None, paths=None, return_format='de_normalized', out=None, workers=12, sink=None,
-                     variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None):
+                     variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None, regrid=None):
         """decode_from_bin for many frames.  Returns a list of HOST float32 arrays [C, H, W] (views of `out`
         [n, C, H, W] when given, fresh arrays otherwise); the D2H of each reconstruction goes through the
         decoding thread's pinned buffer and overlaps the other frames' work.  `sink(i, frame)`: called on the decoding
@@ -689,6 +711,8 @@ class cra5_api:
         coarsen (decode_from_bin): the same shapes as stride=coarsen, every point the area-weighted mean of its coarse
         cell - 1 / (k_lat * k_lon) of the bytes cross the host link; grid_box(region, coarsen=coarsen) gives lat / lon
         and the cells' lat_bnds / lon_bnds.
+        regrid (decode_from_bin): a regrid.Grid - every frame is [C', Ho, Wo] on that target grid, regridded on the device;
+        only the target grid crosses the host link.  `out`, `sink` and `pack` work on the regridded frame.
         residual (decode_from_bin): True - the .res beside every .bin -, or one sidecar path per frame; every frame is
         corrected on the device before it crosses the host link.
         pack (decode_from_bin; only with return_format 'de_normalized'): "int16" / True / {variable: (lo, hi)} - every frame
@@ -698,16 +722,16 @@ class cra5_api:
         scale_factor, add_offset, vmin, vmax, nonfinite, saturated, fill_value; `out` must be a C-contiguous int16 array
         [n, C', Hb, Wb] and q is its view; `sink(i, item)` receives the dict, q a view of the pinned buffer."""
         return self._decode_batch(time_stamps, paths, return_format, out, workers, sink, variables, region, stride, coarsen,
-                                  residual, pack)
+                                  residual, pack, regrid=regrid)
 
     def _decode_batch(self, time_stamps, paths, return_format, out, workers, sink, variables, region, stride, coarsen,
-                      residual, pack, what="decode_batch", per_variable=False):
+                      residual, pack, what="decode_batch", per_variable=False, regrid=None):
         if paths is None:
             paths = [self._bin_path(ts) for ts in time_stamps]
         denorm = self._denorm_arg(return_format)
         self.net._require_gpu()
-        sel = self._select(variables, region, stride, coarsen)
-        sides = self._residual_arg(what, residual, list(paths), return_format, sel.coarsen)
+        sel = self._select(variables, region, stride, coarsen, regrid)
+        sides = self._residual_arg(what, residual, list(paths), return_format, sel.coarsen, sel.regrid)
         pk = self._pack_arg(what, pack, return_format, sel, per_variable)
         self._check_out(out, len(paths), sel.shape, np.int16 if pk is not None else np.float32)
 
@@ -716,7 +740,7 @@ class cra5_api:
                                            list(enumerate(paths)))
 
     def decode_to_nc(self, time_stamps=None, paths=None, save_root=None, pack="int16", variables=None, region=None,
-                     stride=None, coarsen=None, residual=None, workers=12):
+                     stride=None, coarsen=None, residual=None, workers=12, regrid=None):
         """.bin archives back to the NetCDF files the rest of the tool chain reads: decode_batch(pack=...) with a sink that
         writes every frame, on its decoding thread, as {save_root}/ERA5/{yyyy}/{ts}_pressure.nc / {ts}_single.nc in the
         layout read_data_from_nc reads (pack.write_era5_nc: NetCDF-3 64-bit offset, int16 with scale_factor / add_offset /
@@ -729,7 +753,8 @@ class cra5_api:
         name for a pressure variable ("z": every decoded level of z; a single level such as "z_500" is refused) or the
         channel name of a single-level variable ("t2m"; "tp" in the model's tp x 1000).  The pressure selection must be
         rectangular - every selected pressure variable with the same levels in the same order (ValueError, before any
-        decode).  variables / region / stride / coarsen / residual: as in decode_batch.
+        decode).  variables / region / stride / coarsen / residual / regrid: as in decode_batch (with regrid= the files'
+        latitude / longitude are the target grid's).
         Returns one dict per frame: time_stamp, files (the paths written), bytes (their total size)."""
         if time_stamps is None:
             raise ValueError("decode_to_nc needs time_stamps: they name the NetCDF files")
@@ -737,7 +762,7 @@ class cra5_api:
         if paths is not None and len(list(paths)) != len(time_stamps):
             raise ValueError("decode_to_nc: time_stamps and paths must have the same length")
         save_root = save_root or self.local_root
-        sel = self._select(variables, region, stride, coarsen)
+        sel = self._select(variables, region, stride, coarsen, regrid)
 
         def sink(i, item):
             t0 = time.perf_counter()
@@ -745,14 +770,15 @@ class cra5_api:
             self._log("write_nc", t0)
             return dict(time_stamp=time_stamps[i], files=files, bytes=sum(os.path.getsize(p) for p in files))
         return self._decode_batch(time_stamps, paths, 'de_normalized', None, workers, sink, variables, region, stride,
-                                  coarsen, residual, pack, what="decode_to_nc", per_variable=True)
+                                  coarsen, residual, pack, what="decode_to_nc", per_variable=True, regrid=regrid)
 
     def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, sel, spectrum=False, tol=None):
         """One frame of evaluate_batch on the calling frame thread: the truth is staged once into this thread's device
         frame buffer; the reconstruction comes from the in-memory strings (bin_path None) or from `bin_path`, and only
         the per-channel statistics leave the device.  sel.coarsen = (k_lat, k_lon): both frames are coarsened on the device
         by the same kernel (the reconstruction inside its decode, the truth by VAEformer.coarsen_frame) and compared on
-        the coarse grid.  spectrum: the zonal power spectra of the same device pair join the report."""
+        the coarse grid; sel.regrid likewise (VAEformer.regrid_frame), on the target grid.  spectrum: the zonal power
+        spectra of the same device pair join the report."""
         from . import metrics
         if bin_path is None:
             enc, x = self._encode_staged(ts, arr, save_root, write=save_root is not None)
@@ -787,6 +813,11 @@ class cra5_api:
                                      f"{(self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size'])}")
                 # this thread's persistent workspace, like the decode's own buffers: no allocation per frame
                 x = self.net.coarsen_frame(x.contiguous(), sel.coarsen, out=self.net._buf("eval_truth_coarse", sel.shape))
+            if sel.regrid is not None:
+                if (C, H, W) != (self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size']):
+                    raise ValueError(f"{ts}: the truth frame is {(C, H, W)}, the model's grid "
+                                     f"{(self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size'])}")
+                x = self.net.regrid_frame(x.contiguous(), sel.regrid, out=self.net._buf("eval_truth_regrid", sel.shape))
             if x_hat.shape != x.shape:
                 raise ValueError(f"{ts}: the reconstruction is {tuple(x_hat.shape)}, the truth frame {tuple(x.shape)}")
             err = metrics.reconstruction_error(x_hat, x, lat_weights=lat_weights)
@@ -810,7 +841,7 @@ class cra5_api:
         return rep
 
     def evaluate_batch(self, time_stamps, data=None, bins=None, save_root=None, workers=12, lat_weights="era5",
-                       coarsen=None, spectrum=False, max_error=None):
+                       coarsen=None, spectrum=False, max_error=None, regrid=None):
         """Per-variable reconstruction error of many frames, through the frame pipeline, without copying any
         reconstruction to the host.  Truth frames: `data` (a matching list of host arrays / tensors, physical units) or
         the NetCDF files of `time_stamps`.
@@ -826,6 +857,11 @@ class cra5_api:
         both area-averaged on the device (decode_from_bin's coarsen) and compared on the [C, Ho, Wo] grid, "era5" weights
         being latitude_weights(Ho); the reports also carry coarsen, lat and lon of that grid.  compression_ratio stays
         that of the full frame.
+        regrid (a regrid.Grid; not with coarsen=): the error on that target grid - truth and reconstruction are both
+        regridded on the device by the same kernel (the truth by VAEformer.regrid_frame) and compared there; "era5" weights
+        become the grid's area weights (sin north - sin south of every row's cell, mean 1); the reports also carry regrid
+        (the method), lat, lon, lat_bnds and lon_bnds.  spectrum=True then needs a target lon that is uniform and closes the
+        circle, and a supported width.  Not with max_error.
         spectrum=True: every report also carries the zonal power spectra of metrics.zonal_spectrum on the same device
         pair (with coarsen=, the coarse pair): wavenumber int64 [K], power_truth / power_recon / power_error float64
         [C, K] and resolved_wavenumber int64 [C]; only the spectra leave the device.  The compared width (W, or the coarse
@@ -836,13 +872,23 @@ class cra5_api:
         (bin_bytes + res_bytes); compression_ratio stays that of the .bin.  No budget applies here.  With save_root (and
         bins=None) the .res is written beside the .bin."""
         self.net._require_gpu()
-        sel = self._select(coarsen=coarsen)
+        sel = self._select(coarsen=coarsen, regrid=regrid)
         k = sel.coarsen
         tol = self._residual_tol(max_error)
         if tol is not None and k is not None:
             raise ValueError("evaluate_batch: max_error with coarsen= is not supported - the correction belongs before the "
                              "averaging, on the full grid; evaluate the two separately")
+        if tol is not None and sel.regrid is not None:
+            raise ValueError("evaluate_batch: max_error with regrid= is not supported - the correction belongs before the "
+                             "regridding, on the full grid; evaluate the two separately")
         extra = dict(coarsen=k, lat=sel.lat, lon=sel.lon) if k is not None else {}
+        if sel.regrid is not None:
+            extra = {key: v for key, v in sel.meta.items() if key != "variables"}
+            if isinstance(lat_weights, str) and lat_weights == "era5":
+                lat_weights = sel.regrid["area_weights"]
+            if spectrum and not sel.regrid["closes_circle"]:
+                raise ValueError("evaluate_batch(spectrum=True) with regrid=: the target longitudes must be uniform and close "
+                                 "the circle - a zonal spectrum needs whole latitude circles")
         if spectrum:
             Wc = sel.shape[-1]
             if not ops.spectrum_width_ok(Wc):
@@ -874,7 +920,7 @@ class cra5_api:
 
     def aggregate_batch(self, time_stamps=None, paths=None, stats=("mean", "std", "min", "max"), groups=None, ddof=0,
                         variables=None, region=None, stride=None, return_format='de_normalized', workers=12, to_host=True,
-                        coarsen=None, residual=None):
+                        coarsen=None, residual=None, regrid=None):
         """Per-grid-point statistics over time of many decoded frames (a daily or monthly mean, the spread, the extremes),
         reduced on the GPU: every .bin is decoded through the frame pipeline exactly as decode_batch decodes it, and
         instead of crossing the host link the reconstruction is folded into device accumulators (cra5_amd.timestats,
@@ -887,10 +933,11 @@ class cra5_api:
             distinct label, the labels in order of first appearance; within a group the frames apply in index order.
           variables / region / stride / coarsen / return_format ('de_normalized' | 'normalized'): as in decode_batch -
             with coarsen=k the statistics are those of the area-averaged frames, in 1 / (k_lat * k_lon) of the accumulator
-            memory and of the final host copy.
+            memory and of the final host copy; with regrid= (a regrid.Grid) those of the frames on that target grid.
           residual (decode_from_bin): True or one sidecar path per frame - every frame is corrected on the device before
             it is folded in: the statistics are those of the error-bounded frames.
-        Returns a dict: variables, lat, lon (also for the full grid; with coarsen also coarsen, lat_bnds, lon_bnds), n (int; with groups an int64 [G] array), groups
+        Returns a dict: variables, lat, lon (also for the full grid; with coarsen also coarsen, lat_bnds, lon_bnds; with regrid
+        also regrid, lat_bnds, lon_bnds), n (int; with groups an int64 [G] array), groups
         (the labels, when given) and per statistic a HOST float32 array [C', Hb, Wb] ([G, C', Hb, Wb] with groups), or
         with to_host=False a device tensor of that shape.  A frame that fails (a missing file, a StreamDesyncError) ends
         the call with that frame's error."""
@@ -921,8 +968,8 @@ class cra5_api:
             g = counts.index(min(counts))
             raise ValueError(f"aggregate_batch: std with ddof = {ddof} needs more than {ddof} frame(s) per group; "
                              + (f"group {labels[g]!r} holds {counts[g]}" if groups is not None else f"{counts[g]} given"))
-        sel = self._select(variables, region, stride, coarsen)
-        sides = self._residual_arg("aggregate_batch", residual, paths, return_format, sel.coarsen)
+        sel = self._select(variables, region, stride, coarsen, regrid)
+        sides = self._residual_arg("aggregate_batch", residual, paths, return_format, sel.coarsen, sel.regrid)
         self.net._require_gpu()
 
         # every accumulator before the first decode: running out of device memory shows here
@@ -1025,7 +1072,7 @@ class cra5_api:
                     per_channel=side["per_channel"], tol=side["tol"])
 
     @staticmethod
-    def _residual_arg(what, residual, bin_paths, return_format, coarsen):
+    def _residual_arg(what, residual, bin_paths, return_format, coarsen, regrid=None):
         """residual= of the decode methods -> one sidecar path (or None) per frame.  True: the .res beside each .bin."""
         if residual is None or residual is False:
             return [None] * len(bin_paths)
@@ -1035,6 +1082,9 @@ class cra5_api:
         if coarsen is not None:
             raise ValueError(f"{what}: residual= with coarsen= is not supported - the correction belongs before the "
                              "averaging, on points the coarsened decode never materialises")
+        if regrid is not None:
+            raise ValueError(f"{what}: residual= with regrid= is not supported - the correction belongs before the "
+                             "regridding, on points the regridded decode never materialises")
         if residual is True:
             sides = [_res.sidecar_path(p) for p in bin_paths]
         elif isinstance(residual, (str, bytes, os.PathLike)):
@@ -1116,13 +1166,14 @@ class cra5_api:
         with torch.no_grad():
             return self.net.decompress(lstrings, shape, return_format='latent')
 
-    def latent_to_reconstruction(self, y_hat, variables=None, region=None, stride=None, coarsen=None):
-        """cra5_api.py:146-151 (normalised units).  variables / region / stride / coarsen: that subset (decode_from_bin)."""
+    def latent_to_reconstruction(self, y_hat, variables=None, region=None, stride=None, coarsen=None, regrid=None):
+        """cra5_api.py:146-151 (normalised units).  variables / region / stride / coarsen / regrid: that subset, or that
+        target grid (decode_from_bin)."""
         with torch.no_grad():
-            return self.net.decode_latent(y_hat, **self._select(variables, region, stride, coarsen).model)
+            return self.net.decode_latent(y_hat, **self._select(variables, region, stride, coarsen, regrid).model)
 
     def decode_from_bin(self, time_stamp=None, custom_path=None, return_format='de_normalized', to_host=False, out=None,
-                        variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None):
+                        variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None, regrid=None):
         """cra5_api.py:153-192.  `to_host=True` (or `out=` a float32 array of the frame's shape): `x_hat` comes back
         as a HOST numpy array through the pinned staging buffer instead of a device tensor.
         variables: names of channel_vname_mapping() (e.g. ["z_500", "t_850", "t2m"]), output channels in that order;
@@ -1141,6 +1192,12 @@ class cra5_api:
         [C', 121, 240].  Computed on the GPU in fixed float64 arithmetic: bit-identical from run to run, a region's result
         the sub-block of the globe's; NaN / inf in a window propagate.  The dict also carries `coarsen`, `lat_bnds`
         [Hb, 2] (north, south) and `lon_bnds` [Wb, 2] (west, east).
+        regrid: a cra5_amd.regrid.Grid (or its plan) - the full decode on that rectilinear target grid, by bilinear
+        interpolation or first-order conservative remapping (the grid's method; DESIGN.md section 4, "Regridding"), on
+        the GPU in fixed float64 arithmetic: x_hat is [C', Ho, Wo], rows in the grid's own order, and only the target grid
+        crosses the host link.  The un-embed runs on the source box the target needs.  Not together with region / stride
+        / coarsen (the target grid is the region), residual or return_format 'latent' (ValueError).  The dict also carries
+        `regrid` (the method), `lat`, `lon`, `lat_bnds` [Ho, 2] (north, south) and `lon_bnds` [Wo, 2] (west, east).
         residual: None | True (the .res beside the .bin: the same path with the extension replaced; a missing file is an
         error) | a sidecar path, written by encode_era5_as_bin(max_error=...).  Its corrections are added on the GPU, in
         place on the decode's output before it goes anywhere else: every point of the corrected channels is then the truth
@@ -1159,15 +1216,15 @@ class cra5_api:
         residual=True the frame is corrected first and then packed, and the distance to the truth is bounded by the
         sidecar's tolerance plus that packing bound.  Only with return_format 'de_normalized' (ValueError otherwise)."""
         if return_format == 'latent' and (variables is not None or region is not None or stride is not None
-                                          or coarsen is not None):
+                                          or coarsen is not None or regrid is not None):
             raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region / stride / "
-                             "coarsen select a subset of the reconstruction")
+                             "coarsen / regrid select a subset of the reconstruction")
         if return_format != 'latent':
             self._denorm_arg(return_format)
-        sel = self._select(variables, region, stride, coarsen)
+        sel = self._select(variables, region, stride, coarsen, regrid)
         bin_path = custom_path or self._bin_path(time_stamp)
         res_path = self._residual_arg("decode_from_bin", residual if residual is None or isinstance(residual, bool) else [residual],
-                                      [bin_path], return_format, sel.coarsen)[0]
+                                      [bin_path], return_format, sel.coarsen, sel.regrid)[0]
         pk = self._pack_arg("decode_from_bin", pack, return_format, sel)
         stats = None
         decoding_start = time.time()

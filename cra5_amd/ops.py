@@ -729,6 +729,72 @@ def coarsen(x, plan_tables, out=None, chan_map=None):
     return out
 
 
+_REGRID_TABLES = (("row0", torch.int32), ("ntap", torch.int32), ("rw", torch.float64), ("order", torch.int32),
+                  ("col0", torch.int32), ("ctap", torch.int32), ("cw", torch.float64), ("tiles", torch.int32))
+
+
+def regrid_tables(plan, device):
+    """The tables of ops.regrid for a regrid.Grid.plan: its geometry plus device copies of row0 / ntap / order (int32
+    [Ho]), rw (fp64 [Ho, Tmax]), col0 / ctap (int32 [Wo]), cw (fp64 [Wo, Umax]) and the column tiles (int32 [n, 4],
+    regrid.tile_table: computed here, on the host, for the kernel's LDS budget)."""
+    from . import regrid as _rg
+    t = dict(plan)
+    tiles, t["tile_cols"], t["max_span"] = _rg.tile_table(plan)
+    host = dict(plan, tiles=tiles)
+    for k, dt in _REGRID_TABLES:
+        t[k] = torch.as_tensor(np.ascontiguousarray(host[k], dtype=np.float64 if dt == torch.float64 else np.int32)).to(device)
+    return t
+
+
+def regrid(x, tables, out=None, chan_map=None):
+    """cra5_regrid_f32: x - contiguous fp32 [C, Hs, Ws], the source box tables["src_box"] of an H x W global grid -
+    regridded (bilinear or first-order conservative: the plan's tables) onto the plan's target grid -> contiguous fp32
+    [C_out, Ho, Wo] (`out`, or a fresh tensor), rows in the target's own order.  tables: regrid_tables(Grid.plan(H, W),
+    device).  chan_map: as in ops.coarsen.  The arithmetic is fixed (include/cra5_amd.h): bit-identical from run to run,
+    and a sub-grid's result is the sub-block of the whole target grid's."""
+    t = tables
+    _dev(x, out)
+    ok = isinstance(t, dict) and all(isinstance(t.get(k), torch.Tensor) and t[k].is_cuda and t[k].is_contiguous()
+                                     and t[k].dtype == dt for k, dt in _REGRID_TABLES)
+    if not ok:
+        raise ValueError("regrid: tables must come from ops.regrid_tables (row0 / ntap / order / col0 / ctap / tiles int32, "
+                         "rw / cw fp64 contiguous device tensors)")
+    Ho, Wo = int(t["Ho"]), int(t["Wo"])
+    sr0, sr1, sc0, snc = (int(v) for v in t["src_box"])
+    H, W = (int(v) for v in t["grid"])
+    if any(t[k].device != x.device for k, _ in _REGRID_TABLES):
+        raise ValueError(f"regrid: the tables are on {t['row0'].device}, x on {x.device}")
+    if (any(tuple(t[k].shape) != (Ho,) for k in ("row0", "ntap", "order")) or t["rw"].dim() != 2 or t["rw"].shape[0] != Ho
+            or any(tuple(t[k].shape) != (Wo,) for k in ("col0", "ctap")) or t["cw"].dim() != 2 or t["cw"].shape[0] != Wo
+            or t["tiles"].dim() != 2 or t["tiles"].shape[1] != 4 or t["tiles"].shape[0] < 1):
+        raise ValueError(f"regrid: the tables do not belong to a plan of {Ho} x {Wo} target points")
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous() or tuple(x.shape[1:]) != (sr1 - sr0, snc):
+        raise ValueError(f"regrid: x must be a contiguous fp32 [C, {sr1 - sr0}, {snc}] tensor - the plan's source box "
+                         f"{(sr0, sr1, sc0, snc)} (got {tuple(x.shape)} {x.dtype})")
+    C = x.shape[0]
+    if chan_map is not None:
+        if not (isinstance(chan_map, torch.Tensor) and chan_map.is_cuda and chan_map.dtype == torch.int32
+                and chan_map.dim() == 1 and chan_map.is_contiguous() and chan_map.numel() > 0
+                and chan_map.device == x.device):
+            raise ValueError("regrid: chan_map must be a contiguous int32 vector on x's device")
+        C_out = chan_map.numel()
+    else:
+        C_out = C
+    if out is None:
+        out = torch.empty((C_out, Ho, Wo), device=x.device, dtype=torch.float32)
+    if not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (C_out, Ho, Wo)
+            and out.device == x.device):
+        raise ValueError(f"regrid: out must be a contiguous fp32 [{C_out}, {Ho}, {Wo}] tensor on x's device")
+    ev = TIMER.start() if TIMER is not None else None
+    check(lib().cra5_regrid_f32(_p(x), C, sr1 - sr0, snc, sr0, sc0, H, W, Ho, Wo, _p(t["row0"]), _p(t["ntap"]), _p(t["rw"]),
+                                t["rw"].shape[1], _p(t["order"]), _p(t["col0"]), _p(t["ctap"]), _p(t["cw"]),
+                                t["cw"].shape[1], _p(t["tiles"]), t["tiles"].shape[0], int(t["tile_cols"]),
+                                int(t["max_span"]), _p(chan_map), C_out, _p(out), _stream()), "cra5_regrid_f32")
+    if ev is not None:
+        TIMER.stop("regrid", ev, 4.0 * (C_out * (sr1 - sr0) * snc + C_out * Ho * Wo))
+    return out
+
+
 PROBE_PARTIALS = 256     # CRA5_PROBE_PARTIALS
 
 

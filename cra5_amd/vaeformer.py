@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, subset
+from . import regrid as _regrid
 from ._lib import ERR_RANGE, Cra5Error, StreamDesyncError
 from .config import RuntimeConfig, runtime_setting
 from .entropy import EntropyBottleneck, GaussianConditional, get_scale_table
@@ -788,11 +789,13 @@ class VAEformer(nn.Module):
         return params[:L], params[L:]
 
     # ---- g_s --------------------------------------------------------------------------------
-    def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None, coarsen=None):
+    def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None, coarsen=None,
+                      regrid=None):
         """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300).  channels / box / step (canonical, _subset_args):
         the [len(channels), r1 - r0, nc] slice of that frame - thinned to the global rows % s_lat == 0 / columns % s_lon
         == 0 when step = (s_lat, s_lon) -, bit for bit (_unembed).  coarsen = (k_lat, k_lon) (_coarsen_arg; not with a
-        step): the area-weighted mean of that frame at the points step = coarsen would keep (_unembed_coarsened).  out: the
+        step): the area-weighted mean of that frame at the points step = coarsen would keep (_unembed_coarsened).  regrid (a
+        plan, _regrid_arg; on its own): that frame on the plan's target grid (_unembed_regridded).  out: the
         contiguous destination of _decoded_shape (one frame of the caller's batch result) - the un-embed writes x_hat
         there; None: a fresh tensor."""
         cfg = self.cfg
@@ -808,7 +811,7 @@ class VAEformer(nn.Module):
         Cout, (Himg, Wimg) = cfg['out_chans'], cfg['img_size']
         # the LayerNorm writes plain rows when the whole frame's un-embed would take them (a subset's geometry may not)
         h = self._ln(t, self.g_s.norm, f"h{D}", plain=self._fused_unembed_form(Cout, Himg, Wimg)[1])
-        return self._unembed(h, mean, std, channels, box, step, out, coarsen=coarsen)
+        return self._unembed(h, mean, std, channels, box, step, out, coarsen=coarsen, regrid=regrid)
 
     # ---- un-embed: the whole frame, or chosen channels and / or a lat-lon box of it ---------------------------
     # The transformer runs on the whole grid (global attention); everything after the final LayerNorm is local.  The
@@ -863,12 +866,46 @@ class VAEformer(nn.Module):
             subset.kept_points(box if box is not None else (0, H, 0, W), k, W)
         return k
 
-    def _selection_args(self, channels=None, box=None, step=None, coarsen=None):
-        """-> the canonical (channels, box, step, coarsen) of _subset_args, _step_arg and _coarsen_arg, each validated
-        against the ones before it: what _decode_frame and everything below it take."""
+    def _regrid_arg(self, regrid, box=None, step=None, coarsen=None):
+        """Validate a target grid (regrid.Grid | its plan | None) against the canonical box / step / coarsen -> the plan
+        of this model's grid (Grid.plan: built once per grid), or None.  ValueError for anything else, and together with
+        a box, a step or a coarsening factor: the target grid is the region and the resolution."""
+        if regrid is None:
+            return None
+        for name, v in (("box", box), ("step", step), ("coarsen", coarsen)):
+            if v is not None:
+                raise ValueError(f"regrid and {name} {v!r}: pass one of the two - the target grid names the region and "
+                                 f"the resolution itself")
+        H, W = self.cfg['img_size']
+        return _regrid.as_plan(regrid, H, W)
+
+    def _selection_args(self, channels=None, box=None, step=None, coarsen=None, regrid=None):
+        """-> the canonical (channels, box, step, coarsen, regrid) of _subset_args, _step_arg, _coarsen_arg and
+        _regrid_arg, each validated against the ones before it: what _decode_frame and everything below it take."""
         channels, box = self._subset_args(channels, box)
         step = self._step_arg(step, box)
-        return channels, box, step, self._coarsen_arg(coarsen, box, step)
+        coarsen = self._coarsen_arg(coarsen, box, step)
+        return channels, box, step, coarsen, self._regrid_arg(regrid, box, step, coarsen)
+
+    def _regrid_tables(self, plan):
+        """ops.regrid_tables of a canonical plan - built once per target grid, cached like the coarsening tables."""
+        return self._sub_cached(("rplan", self.device, plan["key"]), self, lambda: ops.regrid_tables(plan, self.device))
+
+    def regrid_frame(self, x, grid, out=None):
+        """A whole frame x [C, H, W] (contiguous fp32, on the model's device) on the target grid (regrid.Grid | its plan)
+        -> [C, Ho, Wo]: what a decode with regrid= returns, applied to a frame already on the device (the truth frame of
+        an evaluation)."""
+        self._require_gpu()
+        plan = self._regrid_arg(grid)
+        if plan is None:
+            raise ValueError("regrid_frame: grid must be a regrid.Grid or its plan")
+        H, W = self.cfg['img_size']
+        if x.dim() != 3 or tuple(x.shape[1:]) != (H, W):
+            raise ValueError(f"regrid_frame: x must be a [C, {H}, {W}] frame, got {tuple(x.shape)}")
+        sr0, sr1, sc0, snc = plan["src_box"]
+        if (sr0, sr1, sc0, snc) != (0, H, 0, W):
+            x = ops.crop(x, sr0, sr1 - sr0, sc0, snc, out=self._buf("regrid_frame_src", (x.shape[0], sr1 - sr0, snc)))
+        return ops.regrid(x, self._regrid_tables(plan), out=out)
 
     def _coarsen_tables(self, box, k):
         """(subset.coarsen_plan, ops.coarsen_tables) of the canonical box and factor - built once per (box, k), cached
@@ -927,12 +964,14 @@ class VAEformer(nn.Module):
         return self._sub_cached(("stat", t.data_ptr(), t._version, chans), t,
                                 lambda: t.index_select(0, torch.tensor(chans, device=t.device, dtype=torch.long)))
 
-    def _decoded_shape(self, channels=None, box=None, step=None, coarsen=None):
-        """[C', H', W'] of one decoded frame for the canonical channels / box (_subset_args) and step (_step_arg) or
-        coarsen (_coarsen_arg: the shape of step = coarsen)."""
+    def _decoded_shape(self, channels=None, box=None, step=None, coarsen=None, regrid=None):
+        """[C', H', W'] of one decoded frame for the canonical channels / box (_subset_args) and step (_step_arg),
+        coarsen (_coarsen_arg: the shape of step = coarsen) or regrid (_regrid_arg: the target grid's)."""
         step = step if coarsen is None else coarsen
         H, W = self.cfg['img_size']
         C = len(channels) if channels is not None else self.cfg['out_chans']
+        if regrid is not None:
+            return C, int(regrid["Ho"]), int(regrid["Wo"])
         r0, r1, _, nc = box if box is not None else (0, H, 0, W)
         if step is None:
             return C, r1 - r0, nc
@@ -962,13 +1001,15 @@ class VAEformer(nn.Module):
                  if self.gemm_mode == "split" and self.fused_unembed and D <= 8192 else 0)
         return nside, bool(nside) and self._hi("g_s.final") and self.f16_layout == "plain" and D % 64 == 0
 
-    def _unembed(self, h, mean, std, chans, box, step=None, out=None, coarsen=None):
+    def _unembed(self, h, mean, std, chans, box, step=None, out=None, coarsen=None, regrid=None):
         """The un-embed for channels `chans` (tuple | None: all) inside grid box `box` (tuple | None: the whole grid),
         from the final LayerNorm's output h (SplitMat, or fp32 [N, D] on the exact-f32 engines) -> [C', Hb, Wb], written
         into `out` (_frame_dest: a frame of the caller's batch result - every form below stores straight into it; None:
         a fresh tensor).  chans = box = None is the full decode.  step = (s_lat, s_lon): only the box's points on the
         global lattice rows % s_lat == 0, columns % s_lon == 0 -> [C', Ho, Wo] (_unembed_thinned: the same products, far
-        fewer).  coarsen = (k_lat, k_lon): _unembed_coarsened."""
+        fewer).  coarsen = (k_lat, k_lon): _unembed_coarsened.  regrid (a plan): _unembed_regridded."""
+        if regrid is not None:
+            return self._unembed_regridded(h, mean, std, chans, regrid, out)
         if coarsen is not None:
             return self._unembed_coarsened(h, mean, std, chans, box, coarsen, out)
         if step is not None:
@@ -1123,6 +1164,22 @@ class VAEformer(nn.Module):
         out = self._frame_dest(out, (Cs, plan["Ho"], plan["Wo"]))
         return ops.coarsen(src, tdev, out=out)
 
+    def _unembed_regridded(self, h, mean, std, chans, plan, out=None):
+        """_unembed onto a target grid (a canonical plan of _regrid_arg), on the pattern of _unembed_coarsened: the
+        un-embed runs on the source box the plan's windows need - the hull of all taps, the whole circle when it closes -
+        into a per-thread persistent buffer, de-normalised when mean / std are given (the weights of a row and of a
+        column sum to 1 up to rounding, x * std + mean is affine per channel), and ONE streaming kernel (ops.regrid,
+        csrc/regrid.hip) writes the target grid into `out`.  The source buffer holds exactly the values (bits) the full
+        decode has there."""
+        H, W = self.cfg['img_size']
+        tdev = self._regrid_tables(plan)
+        sb = tuple(int(v) for v in plan["src_box"])
+        Cs = len(chans) if chans is not None else self.cfg['out_chans']
+        src = self._buf("ue_regrid_src", (Cs, sb[1] - sb[0], sb[3]))
+        self._unembed(h, mean, std, chans, None if sb == (0, H, 0, W) else sb, None, out=src)
+        out = self._frame_dest(out, (Cs, plan["Ho"], plan["Wo"]))
+        return ops.regrid(src, tdev, out=out)
+
     # ---- latent side: everything between y and the entropy coder ---------------------------
     def _latent_side_frame(self, y, want_lik=False, z_sym_out=None):
         z = self._h_a_frame(y)
@@ -1235,7 +1292,7 @@ class VAEformer(nn.Module):
             return y, self._finite(flag), None
         return self._range_guard(0, run, "encode")
 
-    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None, out=None, coarsen=None):
+    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None, out=None, coarsen=None, regrid=None):
         """g_s of one frame inside the caller's GPU phase -> (x_hat, pinned probe values: test them with _finite once
         the phase has ended).  The residual stream after the last block carries every upstream poison - token-wise, and
         the global attention spreads it.  The final LayerNorm's split store is O(gamma * sqrt(D)): a checkpoint with
@@ -1243,22 +1300,25 @@ class VAEformer(nn.Module):
         reconstruction itself (every 2053rd pixel: ~14 samples of each token's 268 x 110-pixel patch, ~500 of every
         channel) is probed as well.  A subset decode (channels / box / step) probes the decoded subset itself:
         every output channel sampled at least min(its element count, 500) times - a coarsened decode likewise: a
-        non-finite value of the source stays non-finite through the weighted mean of every window that holds it.  out:
+        non-finite value of the source stays non-finite through the weighted mean of every window that holds it (a
+        regridded decode likewise).  out:
         _decode_frame's destination - the probe reads the frame where it was written."""
         x_hat = self._decode_frame(y_hat, mean=mean, std=std, channels=channels, box=box, step=step, out=out,
-                                   coarsen=coarsen)
+                                   coarsen=coarsen, regrid=regrid)
         D = self.cfg['embed_dim']
-        whole = channels is None and box is None and step is None and coarsen is None
+        whole = channels is None and box is None and step is None and coarsen is None and regrid is None
         stride = 2053 if whole else max(1, (x_hat.numel() // x_hat.shape[0]) // 500)
         return x_hat, self._to_host("ok1", self._probe(self._buf(f"t{D}", (self.Hp * self.Wp, D)), (x_hat, stride)))
 
-    def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None, coarsen=None):
+    def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None, coarsen=None,
+                        regrid=None):
         """g_s of one frame under the range guard: y_hat [L, Hp, Wp] -> x_hat [C, H, W] (or its subset: canonical
-        channels / box of _subset_args, step of _step_arg or coarsen of _coarsen_arg).  out: the frame's destination (_decode_frame); a re-run on
+        channels / box of _subset_args, step of _step_arg, coarsen of _coarsen_arg or regrid of _regrid_arg).  out: the
+        frame's destination (_decode_frame); a re-run on
         the exact-f32 engines overwrites the same destination."""
         def run():
             with self._gpu_phase():
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen, regrid)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, run, "decode")
 
@@ -1289,7 +1349,7 @@ class VAEformer(nn.Module):
         return y, None, None
 
     @torch.no_grad()
-    def decode_latent(self, y, type='quantized', channels=None, box=None, step=None, coarsen=None):
+    def decode_latent(self, y, type='quantized', channels=None, box=None, step=None, coarsen=None, regrid=None):
         """vaeformer.py:294-300.  channels: output channel indices (in the order given); box = (r0, r1, c0, nc): grid rows
         [r0, r1) and nc columns from c0, wrapping at W (subset.grid_box) -> [B, len(channels), r1 - r0, nc], the same
         slice of the full decode bit for bit.  step: a stride, int | (s_lat, s_lon) - of the box (default: the globe) only
@@ -1298,14 +1358,17 @@ class VAEformer(nn.Module):
         full[channels][:, kept_rows][:, :, kept_cols] as bit patterns.  None / 1 / (1, 1): no thinning.
         coarsen: int | (k_lat, k_lon), not together with a step - at the points step = coarsen keeps, the area-weighted
         mean of the full decode over the coarse cell round each (first-order conservative; subset.coarsen_plan, DESIGN.md
-        section 4): fixed float64 arithmetic, a region's result is the sub-block of the globe's bit for bit."""
+        section 4): fixed float64 arithmetic, a region's result is the sub-block of the globe's bit for bit.
+        regrid: a regrid.Grid or its plan, not together with box / step / coarsen - the full decode on that target grid,
+        bilinear or first-order conservative ("Regridding") -> [B, len(channels), Ho, Wo], rows in
+        the grid's own order; fixed float64 arithmetic, a sub-grid's result is the sub-block of the whole grid's."""
         self._require_gpu()
-        channels, box, step, coarsen = self._selection_args(channels, box, step, coarsen)
+        channels, box, step, coarsen, regrid = self._selection_args(channels, box, step, coarsen, regrid)
         # the batch result is allocated once and every frame's un-embed stores into its slice (no stack copy)
-        out = torch.empty((y.shape[0],) + self._decoded_shape(channels, box, step, coarsen), device=self.device,
+        out = torch.empty((y.shape[0],) + self._decoded_shape(channels, box, step, coarsen, regrid), device=self.device,
                           dtype=torch.float32)
         for b in range(y.shape[0]):
-            self._decode_guarded(y[b], channels=channels, box=box, step=step, out=out[b], coarsen=coarsen)
+            self._decode_guarded(y[b], channels=channels, box=box, step=step, out=out[b], coarsen=coarsen, regrid=regrid)
         return out
 
     @torch.no_grad()
@@ -1445,9 +1508,9 @@ class VAEformer(nn.Module):
             "stream or a different checkpoint looks the same.  Nothing was reconstructed", e.status)
 
     def _decompress_frame(self, y_string, z_string, shape, reconstruct, mean=None, std=None, channels=None, box=None,
-                          step=None, out=None, coarsen=None):
+                          step=None, out=None, coarsen=None, regrid=None):
         """host: decode z | GPU: h_s, indexes | host: decode y | GPU: de-quantise (+ g_s: the whole frame, or the
-        canonical channels / box of _subset_args, step of _step_arg or coarsen of _coarsen_arg; out: the
+        canonical channels / box of _subset_args, step of _step_arg, coarsen of _coarsen_arg or regrid of _regrid_arg; out: the
         reconstruction's destination, _decode_frame)."""
         eb, gc = self.entropy_bottleneck, self.gaussian_conditional
         Cz = eb.channels
@@ -1523,30 +1586,34 @@ class VAEformer(nn.Module):
                     y_hat = ops.gaussian_conditional(scales, means, gc.scale_table, sym_in=y_sym, want=("y_hat",))["y_hat"]
                 if not reconstruct:
                     return y_hat, True, None
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen, regrid)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, gpu_side, "decompress")
 
     @torch.no_grad()
-    def decompress(self, strings, shape, return_format='reconstructed', channels=None, box=None, step=None, coarsen=None):
-        """vaeformer.py:378-400.  channels / box / step / coarsen: a subset of the reconstruction (decode_latent)."""
+    def decompress(self, strings, shape, return_format='reconstructed', channels=None, box=None, step=None, coarsen=None,
+                   regrid=None):
+        """vaeformer.py:378-400.  channels / box / step / coarsen / regrid: a subset of the reconstruction, or the
+        reconstruction on another grid (decode_latent)."""
         self._require_gpu()
         assert isinstance(strings, list) and len(strings) == 2
         rec = return_format != 'latent'
-        if not rec and (channels is not None or box is not None or step is not None or coarsen is not None):
-            raise ValueError("decompress: return_format='latent' returns the latent; channels / box / step / coarsen "
-                             "select a subset of the reconstruction")
-        channels, box, step, coarsen = self._selection_args(channels, box, step, coarsen)
+        if not rec and (channels is not None or box is not None or step is not None or coarsen is not None
+                        or regrid is not None):
+            raise ValueError("decompress: return_format='latent' returns the latent; channels / box / step / coarsen / "
+                             "regrid select a subset of the reconstruction")
+        channels, box, step, coarsen, regrid = self._selection_args(channels, box, step, coarsen, regrid)
         self.entropy_bottleneck._check()
         self.gaussian_conditional._check()
         B = len(strings[0])
         if not rec:
             return torch.stack([self._decompress_frame(strings[0][b], strings[1][b], shape, False) for b in range(B)])
         # the batch result is allocated once and every frame's un-embed stores into its slice (no stack copy)
-        out = torch.empty((B,) + self._decoded_shape(channels, box, step, coarsen), device=self.device, dtype=torch.float32)
+        out = torch.empty((B,) + self._decoded_shape(channels, box, step, coarsen, regrid), device=self.device,
+                          dtype=torch.float32)
         for b in range(B):
             self._decompress_frame(strings[0][b], strings[1][b], shape, True, channels=channels, box=box, step=step,
-                                   out=out[b], coarsen=coarsen)
+                                   out=out[b], coarsen=coarsen, regrid=regrid)
         return {"x_hat": out}
 
     @torch.no_grad()

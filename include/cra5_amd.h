@@ -323,6 +323,28 @@ int cra5_coarsen_f32(const float *src, int C_src, int Hs, int Ws, int src_r0, in
                      int out_r0, int k_lat, int Ho, int out_c0, int k_lon, int Wo, const int *row0, const int *ntap,
                      const double *rw, int rw_pitch, const int *chan_map, int C_out, float *dst, void *stream);
 
+/* Regridding onto any rectilinear lat/lon grid (csrc/regrid.hip; cra5_amd/regrid.py Grid.plan):
+ * bilinear interpolation or first-order conservative remapping of src - fp32 [C_src][Hs][Ws], contiguous, whose element
+ * [.][0][0] is the GLOBAL grid point (src_r0, src_c0) of an H x W grid; Ws == W: the whole circle, src_c0 == 0, windows
+ * wrap at the east edge - onto Ho x Wo target points -> dst fp32 [C_out][Ho][Wo], contiguous.  chan_map: as in
+ * cra5_coarsen_f32.  Device tables: row0 / ntap int32 [Ho], rw fp64 [Ho][rw_pitch] - the first global source row, the row
+ * count (<= rw_pitch) and the weights of target row i's window; order int32 [Ho] - the target rows from north to south
+ * (the walk; row order[k] is written); col0 / ctap int32 [Wo], cw fp64 [Wo][cw_pitch] - the same along the columns, window
+ * column u is source column (col0[j] + u) mod W; tiles int32 [n_tiles][4] - (first target column, column count <=
+ * tile_cols, first global source column of the tile's span, span length <= max_span) per column tile.
+ *   inner(h, j)  = sum over u, west to east,   of cw[j][u] * (double)src(h, (col0[j] + u) mod W)
+ *   dst[c][i][j] = (float) sum over t, north to south, of rw[i][t] * inner(row0[i] + t, j)
+ * in float64, every sum from 0, every product and add rounded on its own: bit-identical from run to run, a sub-grid's
+ * result is the sub-block of the whole target grid's.  Non-finite samples propagate (IEEE).  One pass, no atomics, any
+ * 4-byte aligned src / dst.  A table entry that names a row, a column window or a span outside the source is not read:
+ * those outputs become NaN.  CRA5_ERR_ARG, before any device work, for NULL / misaligned pointers (chan_map may be NULL),
+ * sizes <= 0, a source box outside the grid, a box as wide as the grid that does not start at column 0, rw_pitch > H,
+ * cw_pitch > 64 or > W, tile_cols > 256 or tile_cols * cw_pitch > 4096, n_tiles > Wo, max_span > 7936 or > 2 W. */
+int cra5_regrid_f32(const float *src, int C_src, int Hs, int Ws, int src_r0, int src_c0, int H, int W, int Ho, int Wo,
+                    const int *row0, const int *ntap, const double *rw, int rw_pitch, const int *order, const int *col0,
+                    const int *ctap, const double *cw, int cw_pitch, const int *tiles, int n_tiles, int tile_cols,
+                    int max_span, const int *chan_map, int C_out, float *dst, void *stream);
+
 /* Finiteness probe of the range guard: partials[b] = sum of x[i * stride] over block b's share of i = 0 .. ceil(n / stride)
  * - 1, b = 0 .. CRA5_PROBE_PARTIALS - 1 (written, never accumulated: no memset, deterministic).  A partial is non-finite as
  * soon as one addend is; the caller copies the partials to the host with the phase's other results and tests them there. */
