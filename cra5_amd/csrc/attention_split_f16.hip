@@ -249,7 +249,8 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
   // Reduced-precision mode: Q is pre-scaled by scale * log2 e ONCE (one more f16 rounding, inside the mode's tolerance)
   // and the first score MFMA of a tile takes -m_run as its C operand, so the accumulator IS the exponent:
   // p = exp2(acc), no v_fma per score (16 VALU fewer per key tile; the fp32-accurate form has no 16 registers to spare
-  // for the -m vector - DESIGN.md section 9).  VALU time is wall time on this chip's SIMDs.
+  // for the -m vector - DESIGN.md section 9).  The VALU of a tile shares one issue port with the MFMAs of the SIMD's three
+  // waves: what does not fit behind a wave's own MFMAs is wall time (profiles/attn_gap_schedule.txt), so fewer is shorter.
   f32x16 negm;
 #pragma unroll
   for (int r = 0; r < 16; ++r) negm[r] = 0.f;
@@ -515,6 +516,148 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
       m_run = m_new;
     }
     const float m_new = m_run;   // reference point of this tile's exponentials
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (!HI) {
+      // fp32-accurate form: the tile's 24 MFMAs with its vector work HAND-PLACED behind them.  One wave's stream hides
+      // about 24 issue cycles of vector instructions behind a 32-cycle MFMA (plain VALU 4, v_exp_f32 8, the MFMA itself
+      // holds the port for 8); left to hipcc the same instructions came out as gaps of up to 68 cycles beside 10 empty
+      // ones (tools/attn_gap_model.py, profiles/attn_gap_schedule.txt).  A STAGE is one MFMA and what follows it, fenced
+      // with sched_barrier(0) on both sides of the MFMA so that nothing moves across.  Scores (r, r + 1) are a pair unit
+      // u = r / 2, cut into EXP(u): 2 v_fma + 2 v_exp, and SPLIT(u): the 2 adds into psum (r = 0 .. 15 in order, as
+      // ever), v_cvt_pk hi, the 2 v_fma_mix, v_cvt_pk lo - 24 cycles each.
+      //   score MFMAs 0-11 (tile j + 1; they depend on none of this):  EXP 0-5 and SPLIT 0-5, the K fragment reads of
+      //                    steps 2, 3 and the V fragment reads of t = 0
+      //   PV t = 0, MFMAs 12-17 (need units 0-3):  EXP 6-7, SPLIT 6-7, l_run, the V fragment reads of t = 1
+      //   PV t = 1, MFMAs 18-23 (need units 4-7):  tile j + 1's max (its 12 score MFMAs are six stages back)
+      // Arithmetic and its order are those of the loop this replaces: same bits.  What it bought (three waves per SIMD,
+      // whose MFMA and VALU do co-execute: a VALU instruction beside 44 % of the MFMA-busy cycles before, 49 % now): 2 %
+      // of the whole-grid launch, 5 % of a windowed key step - the partner waves already filled most of a wave's gaps.
+#define CRA5_FENCE() __builtin_amdgcn_sched_barrier(0)
+#define CRA5_STAGE(MFMA_STMT) \
+  CRA5_FENCE();               \
+  MFMA_STMT;                  \
+  CRA5_FENCE();
+#define CRA5_KFRAG(PLANE, ST) (*reinterpret_cast<const half8 *>(k_base + kb * KBUF + (PLANE)*KPL + 16 * (ST)))
+#define CRA5_MM(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16((A), (B), (C), 0, 0, 0)
+      typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+      float p[16], psum = 0.f;
+      u32x4 phw[2], plw[2];   // P hi / lo of t = 0, 1: one dword (two keys) per pair unit
+      // (two scores per v_pk_fma_f32 / v_pk_add_f32 instead of scalar fma + add: 16 VALU fewer per tile in the ISA and
+      // NOT faster - global 1.39 vs 1.41 ms, windowed 4 % slower: the packed fp32 ops take two issue slots)
+      auto exp_half = [&](const int u) __attribute__((always_inline)) {
+        p[2 * u] = __builtin_amdgcn_exp2f(fmaf(s_cur[2 * u], cexp, -m_new));
+        p[2 * u + 1] = __builtin_amdgcn_exp2f(fmaf(s_cur[2 * u + 1], cexp, -m_new));
+      };
+      // p -> (hi, lo) with lo = p - f32(hi) as ONE v_fma_mix_f32 that reads the f16 half in place (no v_cvt_f32_f16 +
+      // v_sub per element).  Only the fma_mix is inline asm (hipcc folds fma(x, -1, p) back into a subtraction); the
+      // conversions on both sides stay compiler-generated, so the registers the PV MFMAs read are written by
+      // instructions whose MFMA wait states the hazard recogniser knows.
+      // No s_nop in front of the pair any more: gfx950 wants ONE wait state between a transcendental and a VALU that
+      // reads its result (without it one of four window shapes produced garbage), and any instruction issued in between is one (hipcc's own stream: `v_exp v0; v_mov ..; v_mul
+      // .., v0` without a pad, `s_nop 0` only where the reader follows directly).  hipcc pads for its own instructions,
+      // not for inline asm - so the layout does: SPLIT(u) always sits at least one whole stage behind EXP(u), with that
+      // stage's fenced MFMA, a vector instruction, in between wherever hipcc puts the rest.
+      auto split_half = [&](const int u) __attribute__((always_inline)) {
+        const int r = 2 * u;
+        const half2v h2 = {(_Float16)p[r], (_Float16)p[r + 1]};
+        const unsigned hh = __builtin_bit_cast(unsigned, h2);
+        float d0, d1;
+        asm("v_fma_mix_f32 %0, %2, -1.0, %3 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mix_f32 %1, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+            : "=&v"(d0), "=&v"(d1) : "v"(hh), "v"(p[r]), "v"(p[r + 1]));
+        psum += p[r];
+        psum += p[r + 1];
+        const half2v l2 = {(_Float16)d0, (_Float16)d1};
+        unsigned ll = __builtin_bit_cast(unsigned, l2);
+        asm("" : "+v"(ll));   // (pins the v_cvt_pk to THIS stage: hipcc otherwise sinks all four of a t to the last unit's)
+        phw[u >> 2][u & 3] = hh;
+        plw[u >> 2][u & 3] = ll;
+      };
+#define ph(T) __builtin_bit_cast(half8, phw[T])
+#define pl(T) __builtin_bit_cast(half8, plw[T])
+      half8 vh[2], vl[2];
+      auto v_frag = [&](const int t, const int plane, const int dt) __attribute__((always_inline)) {
+        const unsigned short *vp = v_base + vb * VBUF + plane * VPL + 16 * t * VS + 32 * dt;
+        const half4 a0 = CRA5_TR_READ(vp);
+        const half4 a1 = CRA5_TR_READ(vp + 8 * VS);
+        return __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
+      };
+      // (past the last tile the scores of a stale K buffer are computed and discarded.)
+      half8 kh0 = CRA5_KFRAG(0, 0), kl0 = CRA5_KFRAG(1, 0), kh1 = CRA5_KFRAG(0, 1), kl1 = CRA5_KFRAG(1, 1);
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+      CRA5_STAGE(acc = CRA5_MM(kl0, qh[0], acc))
+      exp_half(0);
+      CRA5_STAGE(acc = CRA5_MM(kh0, ql[0], acc))
+      exp_half(1);
+      CRA5_STAGE(acc = CRA5_MM(kh0, qh[0], acc))
+      split_half(0);
+      const half8 kh2 = CRA5_KFRAG(0, 2), kl2 = CRA5_KFRAG(1, 2);
+      CRA5_STAGE(acc = CRA5_MM(kl1, qh[1], acc))
+      exp_half(2);
+      CRA5_STAGE(acc = CRA5_MM(kh1, ql[1], acc))
+      split_half(1);
+      CRA5_STAGE(acc = CRA5_MM(kh1, qh[1], acc))
+      exp_half(3);
+      const half8 kh3 = CRA5_KFRAG(0, 3), kl3 = CRA5_KFRAG(1, 3);
+      CRA5_STAGE(acc = CRA5_MM(kl2, qh[2], acc))
+      split_half(2);
+      CRA5_STAGE(acc = CRA5_MM(kh2, ql[2], acc))
+      exp_half(4);
+      CRA5_STAGE(acc = CRA5_MM(kh2, qh[2], acc))
+      split_half(3);
+      CRA5_STAGE(acc = CRA5_MM(kl3, qh[3], acc))
+      exp_half(5);
+      vl[0] = v_frag(0, 1, 0);
+      vl[1] = v_frag(0, 1, 1);
+      CRA5_STAGE(acc = CRA5_MM(kh3, ql[3], acc))
+      split_half(4);
+      CRA5_STAGE(acc = CRA5_MM(kh3, qh[3], acc))
+      split_half(5);
+      vh[0] = v_frag(0, 0, 0);
+      vh[1] = v_frag(0, 0, 1);
+      s_next = acc;
+      // ---- O^T += V^T . P^T
+      CRA5_STAGE(o[0] = CRA5_MM(vl[0], ph(0), o[0]))
+      exp_half(6);
+      CRA5_STAGE(o[1] = CRA5_MM(vl[1], ph(0), o[1]))
+      exp_half(7);
+      CRA5_STAGE(o[0] = CRA5_MM(vh[0], pl(0), o[0]))
+      split_half(6);
+      CRA5_STAGE(o[1] = CRA5_MM(vh[1], pl(0), o[1]))
+      split_half(7);
+      vl[0] = v_frag(1, 1, 0);
+      vl[1] = v_frag(1, 1, 1);
+      CRA5_STAGE(o[0] = CRA5_MM(vh[0], ph(0), o[0]))
+      l_run += psum;
+      CRA5_STAGE(o[1] = CRA5_MM(vh[1], ph(0), o[1]))
+      vh[0] = v_frag(1, 0, 0);
+      vh[1] = v_frag(1, 0, 1);
+      // tile j + 1's max in three pieces (CRA5_TILE_MAX, same tree)
+      CRA5_STAGE(o[0] = CRA5_MM(vl[0], ph(1), o[0]))
+      const float ma = CRA5_MAX3(s_next[0], s_next[1], s_next[2]), mb = CRA5_MAX3(s_next[3], s_next[4], s_next[5]);
+      const float mc = CRA5_MAX3(s_next[6], s_next[7], s_next[8]), md = CRA5_MAX3(s_next[9], s_next[10], s_next[11]);
+      const float me = CRA5_MAX3(s_next[12], s_next[13], s_next[14]);
+      CRA5_STAGE(o[1] = CRA5_MM(vl[1], ph(1), o[1]))
+      const float mf = CRA5_MAX3(ma, mb, mc), mg = CRA5_MAX3(md, me, s_next[15]);
+      const float mfg = CRA5_MAX2_VALU(mf, mg);
+      CRA5_STAGE(o[0] = CRA5_MM(vh[0], pl(1), o[0]))
+      const float mx = CRA5_XHALF_MAX(mfg);
+      CRA5_STAGE(o[1] = CRA5_MM(vh[1], pl(1), o[1]))
+      mloc = mx * cmax;   // cexp > 0: max commutes with the scale
+      CRA5_STAGE(o[0] = CRA5_MM(vh[0], ph(1), o[0]))
+      CRA5_STAGE(o[1] = CRA5_MM(vh[1], ph(1), o[1]))
+#undef ph
+#undef pl
+#undef CRA5_MM
+#undef CRA5_KFRAG
+#undef CRA5_STAGE
+#undef CRA5_FENCE
+    } else
+#endif
+    {
     // ---- tile j+1's 12 score MFMAs, interleaved with tile j's softmax VALU work
     // (past the last tile the scores of a stale K buffer are computed and discarded.)
     CRA5_SCORES(s_next, kb);
@@ -555,37 +698,6 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int e = 0; e < 8; ++e) pl[t][e] = (_Float16)0.0f;
-    } else
-    // p -> (hi, lo) with lo = p - f32(hi) as ONE v_fma_mix_f32 that reads the f16 half in place (no
-    // v_cvt_f32_f16 + v_sub per element): 4 VALU per two scores instead of 7.  MFMA and VALU of the waves of a
-    // SIMD do not overlap on this chip: every VALU removed here is wall time.  Only the
-    // fma_mix is inline asm (hipcc folds fma(x, -1, p) back into a subtraction); the conversions on both sides
-    // stay compiler-generated, so the registers the PV MFMAs read are written by instructions whose MFMA
-    // wait states the hazard recogniser knows.
-    {
-      typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-      // (two scores per v_pk_fma_f32 / v_pk_add_f32 instead of scalar fma + add: 16 VALU fewer per tile in the ISA and
-      // NOT faster - global 1.39 vs 1.41 ms, windowed 4 % slower: the packed fp32 ops take two issue slots)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const float p0 = __builtin_amdgcn_exp2f(fmaf(s_cur[r], cexp, -m_new));
-        const float p1 = __builtin_amdgcn_exp2f(fmaf(s_cur[r + 1], cexp, -m_new));
-        psum += p0;
-        psum += p1;
-        const half2v h2 = {(_Float16)p0, (_Float16)p1};
-        const unsigned hh = __builtin_bit_cast(unsigned, h2);
-        float d0, d1;
-        // (s_nop: p0 / p1 come out of v_exp_f32, and gfx950 needs a wait state between a transcendental and a
-        // VALU that reads its result - inserted by hipcc for its own instructions, not for inline asm: without
-        // it one of four window shapes produced garbage)
-        asm("s_nop 0\n\tv_fma_mix_f32 %0, %2, -1.0, %3 op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mix_f32 %1, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-            : "=&v"(d0), "=&v"(d1) : "v"(hh), "v"(p0), "v"(p1));
-        ph[r >> 3][r & 7] = h2[0];
-        ph[r >> 3][(r & 7) + 1] = h2[1];
-        pl[r >> 3][r & 7] = (_Float16)d0;
-        pl[r >> 3][(r & 7) + 1] = (_Float16)d1;
-      }
     }
 #else   /* host pass: the same arithmetic without the inline asm (never executed) */
 #pragma unroll
@@ -623,7 +735,8 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 ? 1 : (NW == 4 ? 3 : 2))) void wi
       o[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[0], ph[t], o[0], 0, 0, 0);
       o[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[1], ph[t], o[1], 0, 0, 0);
     }
-    if (!HI) mloc = CRA5_TILE_MAX(s_next);
+    if (!HI) mloc = CRA5_TILE_MAX(s_next);   // (host pass only: the device's fp32-accurate form is the staged body)
+    }
     }
     // K(j+2) -> the buffer tile j's scores came from (last read before the previous barrier),
     // V(j+1) -> the other V buffer (past the end: stale data into buffers nobody reads);
