@@ -10,7 +10,14 @@
 // the hyper-prior path, whose engine is pinned on both sides of the codec.  Out-of-range activations can therefore
 // never degrade a frame quietly, and the in-range path carries no range-handling instruction at all (the saturating
 // form cost a v_med3 + a v_fma per element in every producer).  In-range values split exactly as before (bit-identical
-// streams).  NaN / inf inputs stay non-finite by the same arithmetic.  Builds with
+// streams).  NaN / inf inputs stay non-finite by the same arithmetic.
+// What a consumer promises (tests/test_poison_gpu.py holds every one of them to it, element by element): the consumers
+// that read BOTH planes turn the pair into NaN in every output that reads it, and change no other output bit.  The
+// reduced-precision consumers (hi_only, plain rows) read the hi plane alone, a bare +-inf: a GEMM row comes out +-inf by
+// the sign of the weights (NaN through 0 * inf or gelu(-inf)), and an attention score q_d * (+-inf) is +-inf by sign -
+// the rows with a NaN or +inf score come out non-finite, a row whose score with that key is -inf gives the key the
+// weight exp2(-inf) = 0 and stays finite.  One non-finite row is all the probe needs; with random-sign q_d a quarter of
+// a window's rows and more are of that kind.  Builds with
 // -DCRA5_RANGE_CHECK (python -m cra5_amd.build --flavour rangecheck) additionally count, per
 // producer call site, the elements with |x| >= 65 504 and the non-finite ones
 // (cra5_debug_range_counts in the C ABI): the evidence that a checkpoint's activations stay

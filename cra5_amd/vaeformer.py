@@ -1295,7 +1295,10 @@ class VAEformer(nn.Module):
     def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None, out=None, coarsen=None, regrid=None):
         """g_s of one frame inside the caller's GPU phase -> (x_hat, pinned probe values: test them with _finite once
         the phase has ended).  The residual stream after the last block carries every upstream poison - token-wise, and
-        the global attention spreads it.  The final LayerNorm's split store is O(gamma * sqrt(D)): a checkpoint with
+        the global attention spreads it (element by element: tests/test_poison_gpu.py.  The one case that is by sign and
+        not by construction: a reduced-precision K element beyond the f16 range is a bare +-inf, and only the queries
+        whose score with that key is NaN or +inf turn non-finite - csrc/split.h).
+        The final LayerNorm's split store is O(gamma * sqrt(D)): a checkpoint with
         |gamma| sqrt(D) >= 65 504, or a non-finite mean / std, poisons x_hat BEHIND that probe - a strided sample of the
         reconstruction itself (every 2053rd pixel: ~14 samples of each token's 268 x 110-pixel patch, ~500 of every
         channel) is probed as well.  A subset decode (channels / box / step) probes the decoded subset itself:

@@ -393,9 +393,11 @@ def eps_terms(family, hd, nt, pieces=0):
     return 12 + hd // 4, 2, (8 + 2 * nt + per_wave + 7) + (4 + 2 * per_wave + 7 + 2) + 3, (1.0, FLT_MIN, FLT_MIN)
 
 
-def reference_and_bound(planes, pad_planes, wins, heads, family, pieces=0, rows=None):
+def reference_and_bound(planes, pad_planes, wins, heads, family, pieces=0, rows=None, drop=None):
     """(ref float64 [N, C], B float64 [N, C]) of the windowed softmax(q k^T hd^-0.5) v with the pad rule (pad positions
     carry the pad row, unmasked), from the operands as stored.  rows: restrict to these token rows (others: 0 / inf).
+    drop: bool [windows, L] - window-local keys that take no part (score -inf: weight 0, none of A_i either; their
+    stored k rows are not read, so they may hold non-finite values) - the softmax without them, same bound.
 
     B[i, d] = 2 (a A_i ln 2 + x) u D_id + 2 e u sum_j w_ij |v_jd| + 2 sub_id + 2^-126      (a, x, e: eps_terms)
     D_id = sum_j w_ij |v_jd - ref_id|.  The first term: an error of the exponent (or of exp2, or the f16 rounding of p in
@@ -415,7 +417,7 @@ def reference_and_bound(planes, pad_planes, wins, heads, family, pieces=0, rows=
     ref = torch.zeros(N, C, dtype=torch.float64, device=hi.device)
     B = torch.full((N, C), float("inf"), dtype=torch.float64, device=hi.device)
     keep = None if rows is None else torch.zeros(N + 1, dtype=torch.bool).index_fill_(0, torch.as_tensor(rows), True).numpy()
-    for idx, real, ph, pl in X.window_operands(planes, pad_planes, wins, heads):
+    for w, (idx, real, ph, pl) in enumerate(X.window_operands(planes, pad_planes, wins, heads)):
         sel = real if keep is None else real & keep[idx]
         if not sel.any():
             continue
@@ -424,8 +426,14 @@ def reference_and_bound(planes, pad_planes, wins, heads, family, pieces=0, rows=
         q, k, v = x[0][:, ts], x[1], x[2]
         L = k.shape[1]
         a, x_, e, (sub_scale, sub_num, sub_den) = eps_terms(family, hd, -(-L // 32), pieces)
+        gone = None if drop is None or not drop[w].any() else torch.from_numpy(drop[w]).to(hi.device)
+        if gone is not None:
+            k = torch.where(gone[None, :, None], torch.zeros_like(k), k)
         t = (q @ k.transpose(-1, -2)) * c
-        A = ((q.abs() @ k.abs().transpose(-1, -2)) * c).amax(-1, keepdim=True)
+        A = (q.abs() @ k.abs().transpose(-1, -2)) * c
+        if gone is not None:
+            t = torch.where(gone[None, None, :], torch.full_like(t, float("-inf")), t)
+        A = A.amax(-1, keepdim=True)
         rho = torch.exp2(t - t.amax(-1, keepdim=True))
         lam = rho.sum(-1, keepdim=True)
         w = rho / lam
