@@ -807,17 +807,15 @@ class cra5_api:
             t_m = time.perf_counter()
             C, H, W = x.shape[-3:]
             x = x.reshape(C, H, W)
-            if sel.coarsen is not None:
+            for arg, frame, buf in ((sel.coarsen, self.net.coarsen_frame, "eval_truth_coarse"),
+                                    (sel.regrid, self.net.regrid_frame, "eval_truth_regrid")):
+                if arg is None:
+                    continue
                 if (C, H, W) != (self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size']):
                     raise ValueError(f"{ts}: the truth frame is {(C, H, W)}, the model's grid "
                                      f"{(self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size'])}")
                 # this thread's persistent workspace, like the decode's own buffers: no allocation per frame
-                x = self.net.coarsen_frame(x.contiguous(), sel.coarsen, out=self.net._buf("eval_truth_coarse", sel.shape))
-            if sel.regrid is not None:
-                if (C, H, W) != (self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size']):
-                    raise ValueError(f"{ts}: the truth frame is {(C, H, W)}, the model's grid "
-                                     f"{(self.net.cfg['out_chans'],) + tuple(self.net.cfg['img_size'])}")
-                x = self.net.regrid_frame(x.contiguous(), sel.regrid, out=self.net._buf("eval_truth_regrid", sel.shape))
+                x = frame(x.contiguous(), arg, out=self.net._buf(buf, sel.shape))
             if x_hat.shape != x.shape:
                 raise ValueError(f"{ts}: the reconstruction is {tuple(x_hat.shape)}, the truth frame {tuple(x.shape)}")
             err = metrics.reconstruction_error(x_hat, x, lat_weights=lat_weights)

@@ -669,14 +669,85 @@ def crop(src, r0, Hb, c0, Wb, out=None):
     return out
 
 
+_COARSEN_TABLES = (("row0", torch.int32), ("ntap", torch.int32), ("rw", torch.float64))
+_REGRID_TABLES = _COARSEN_TABLES + (("order", torch.int32), ("col0", torch.int32), ("ctap", torch.int32),
+                                    ("cw", torch.float64), ("tiles", torch.int32))
+# per operator: its device tables, where they come from, what their plan counts (the words of two messages)
+_WINDOW_OPS = {
+    "coarsen": (_COARSEN_TABLES, "plan_tables must come from ops.coarsen_tables (row0 / ntap int32, rw fp64 contiguous "
+                "device tensors)", "{Ho} output rows"),
+    "regrid": (_REGRID_TABLES, "tables must come from ops.regrid_tables (row0 / ntap / order / col0 / ctap / tiles int32, "
+               "rw / cw fp64 contiguous device tensors)", "{Ho} x {Wo} target points"),
+}
+
+
+def _device_tables(plan, host, spec, device):
+    """dict(plan) with device copies of the host arrays host[name] for every (name, dtype) of spec."""
+    t = dict(plan)
+    for k, dt in spec:
+        t[k] = torch.as_tensor(np.ascontiguousarray(host[k], dtype=np.float64 if dt == torch.float64 else np.int32)).to(device)
+    return t
+
+
 def coarsen_tables(plan, device):
     """The tables of ops.coarsen for a subset.coarsen_plan: its geometry plus device copies of row0 / ntap (int32 [Ho])
     and rw (fp64 [Ho, k_lat + 1])."""
-    t = dict(plan)
-    t["row0"] = torch.as_tensor(np.ascontiguousarray(plan["row0"], dtype=np.int32)).to(device)
-    t["ntap"] = torch.as_tensor(np.ascontiguousarray(plan["ntap"], dtype=np.int32)).to(device)
-    t["rw"] = torch.as_tensor(np.ascontiguousarray(plan["rw"], dtype=np.float64)).to(device)
-    return t
+    return _device_tables(plan, plan, _COARSEN_TABLES, device)
+
+
+def regrid_tables(plan, device):
+    """The tables of ops.regrid for a regrid.Grid.plan: its geometry plus device copies of row0 / ntap / order (int32
+    [Ho]), rw (fp64 [Ho, Tmax]), col0 / ctap (int32 [Wo]), cw (fp64 [Wo, Umax]) and the column tiles (int32 [n, 4],
+    regrid.tile_table: computed here, on the host, for the kernel's LDS budget)."""
+    from . import regrid as _rg
+    tiles, tile_cols, max_span = _rg.tile_table(plan)
+    return _device_tables(dict(plan, tile_cols=tile_cols, max_span=max_span), dict(plan, tiles=tiles), _REGRID_TABLES, device)
+
+
+def _window_reduce(what, x, t, out, chan_map, launch):
+    """The body of ops.coarsen / ops.regrid (`what`; csrc/window_reduce.hip): the device tables `t` against the
+    operator's (name, dtype) spec and the plan's Ho / Wo, x against the plan's source box, chan_map, `out` (allocated
+    when None), then launch(C, C_out, out, (sr0, Hs, sc0, Ws), (H, W)) inside the timer bracket."""
+    spec, origin, belong = _WINDOW_OPS[what]
+    _dev(x, out)
+    ok = isinstance(t, dict) and all(isinstance(t.get(k), torch.Tensor) and t[k].is_cuda and t[k].is_contiguous()
+                                     and t[k].dtype == dt for k, dt in spec)
+    if not ok:
+        raise ValueError(f"{what}: {origin}")
+    Ho, Wo = int(t["Ho"]), int(t["Wo"])
+    sr0, sr1, sc0, snc = (int(v) for v in t["src_box"])
+    H, W = (int(v) for v in t["grid"])
+    if any(t[k].device != x.device for k, _ in spec):
+        raise ValueError(f"{what}: the tables are on {t['row0'].device}, x on {x.device}")
+
+    def belongs(k):       # rw / cw are matrices, tiles [n, 4], the others vectors; first dimension Ho (rows) or Wo (columns)
+        if k == "tiles":
+            return t[k].dim() == 2 and t[k].shape[1] == 4 and t[k].shape[0] >= 1
+        return t[k].dim() == (2 if k in ("rw", "cw") else 1) and t[k].shape[0] == (Wo if k in ("col0", "ctap", "cw") else Ho)
+    if not all(belongs(k) for k, _ in spec):
+        raise ValueError(f"{what}: the tables do not belong to a plan of {belong.format(Ho=Ho, Wo=Wo)}")
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous() or tuple(x.shape[1:]) != (sr1 - sr0, snc):
+        raise ValueError(f"{what}: x must be a contiguous fp32 [C, {sr1 - sr0}, {snc}] tensor - the plan's source box "
+                         f"{(sr0, sr1, sc0, snc)} (got {tuple(x.shape)} {x.dtype})")
+    C = x.shape[0]
+    if chan_map is not None:
+        if not (isinstance(chan_map, torch.Tensor) and chan_map.is_cuda and chan_map.dtype == torch.int32
+                and chan_map.dim() == 1 and chan_map.is_contiguous() and chan_map.numel() > 0
+                and chan_map.device == x.device):
+            raise ValueError(f"{what}: chan_map must be a contiguous int32 vector on x's device")
+        C_out = chan_map.numel()
+    else:
+        C_out = C
+    if out is None:
+        out = torch.empty((C_out, Ho, Wo), device=x.device, dtype=torch.float32)
+    if not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (C_out, Ho, Wo)
+            and out.device == x.device):
+        raise ValueError(f"{what}: out must be a contiguous fp32 [{C_out}, {Ho}, {Wo}] tensor on x's device")
+    ev = TIMER.start() if TIMER is not None else None
+    launch(C, C_out, out, (sr0, sr1 - sr0, sc0, snc), (H, W))
+    if ev is not None:
+        TIMER.stop(what, ev, 4.0 * (C_out * (sr1 - sr0) * snc + C_out * Ho * Wo))
+    return out
 
 
 def coarsen(x, plan_tables, out=None, chan_map=None):
@@ -687,63 +758,15 @@ def coarsen(x, plan_tables, out=None, chan_map=None):
     in order.  The arithmetic is fixed (include/cra5_amd.h): bit-identical from run to run, and a region's result is
     the sub-block of the globe's."""
     t = plan_tables
-    _dev(x, out)
-    ok = (isinstance(t, dict) and all(isinstance(t.get(k), torch.Tensor) and t[k].is_cuda and t[k].is_contiguous()
-                                      for k in ("row0", "ntap", "rw"))
-          and t["row0"].dtype == torch.int32 and t["ntap"].dtype == torch.int32 and t["rw"].dtype == torch.float64)
-    if not ok:
-        raise ValueError("coarsen: plan_tables must come from ops.coarsen_tables (row0 / ntap int32, rw fp64 contiguous "
-                         "device tensors)")
-    Ho, Wo = int(t["Ho"]), int(t["Wo"])
-    ky, kx = (int(v) for v in t["k"])
-    sr0, sr1, sc0, snc = (int(v) for v in t["src_box"])
-    H, W = (int(v) for v in t["grid"])
-    if any(t[k].device != x.device for k in ("row0", "ntap", "rw")):
-        raise ValueError(f"coarsen: the tables are on {t['row0'].device}, x on {x.device}")
-    if tuple(t["row0"].shape) != (Ho,) or tuple(t["ntap"].shape) != (Ho,) or t["rw"].dim() != 2 or t["rw"].shape[0] != Ho:
-        raise ValueError(f"coarsen: the tables do not belong to a plan of {Ho} output rows")
-    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous() or tuple(x.shape[1:]) != (sr1 - sr0, snc):
-        raise ValueError(f"coarsen: x must be a contiguous fp32 [C, {sr1 - sr0}, {snc}] tensor - the plan's source box "
-                         f"{(sr0, sr1, sc0, snc)} (got {tuple(x.shape)} {x.dtype})")
-    C = x.shape[0]
-    if chan_map is not None:
-        if not (isinstance(chan_map, torch.Tensor) and chan_map.is_cuda and chan_map.dtype == torch.int32
-                and chan_map.dim() == 1 and chan_map.is_contiguous() and chan_map.numel() > 0
-                and chan_map.device == x.device):
-            raise ValueError("coarsen: chan_map must be a contiguous int32 vector on x's device")
-        C_out = chan_map.numel()
-    else:
-        C_out = C
-    if out is None:
-        out = torch.empty((C_out, Ho, Wo), device=x.device, dtype=torch.float32)
-    if not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (C_out, Ho, Wo)
-            and out.device == x.device):
-        raise ValueError(f"coarsen: out must be a contiguous fp32 [{C_out}, {Ho}, {Wo}] tensor on x's device")
-    ev = TIMER.start() if TIMER is not None else None
-    check(lib().cra5_coarsen_f32(_p(x), C, sr1 - sr0, snc, sr0, sc0, H, W, 1 if (sc0 == 0 and snc == W) else 0,
-                                 int(t["rows"][0]), ky, Ho, int(t["cols"][0]), kx, Wo, _p(t["row0"]), _p(t["ntap"]),
-                                 _p(t["rw"]), t["rw"].shape[1], _p(chan_map), C_out, _p(out), _stream()),
-          "cra5_coarsen_f32")
-    if ev is not None:
-        TIMER.stop("coarsen", ev, 4.0 * (C_out * (sr1 - sr0) * snc + C_out * Ho * Wo))
-    return out
 
-
-_REGRID_TABLES = (("row0", torch.int32), ("ntap", torch.int32), ("rw", torch.float64), ("order", torch.int32),
-                  ("col0", torch.int32), ("ctap", torch.int32), ("cw", torch.float64), ("tiles", torch.int32))
-
-
-def regrid_tables(plan, device):
-    """The tables of ops.regrid for a regrid.Grid.plan: its geometry plus device copies of row0 / ntap / order (int32
-    [Ho]), rw (fp64 [Ho, Tmax]), col0 / ctap (int32 [Wo]), cw (fp64 [Wo, Umax]) and the column tiles (int32 [n, 4],
-    regrid.tile_table: computed here, on the host, for the kernel's LDS budget)."""
-    from . import regrid as _rg
-    t = dict(plan)
-    tiles, t["tile_cols"], t["max_span"] = _rg.tile_table(plan)
-    host = dict(plan, tiles=tiles)
-    for k, dt in _REGRID_TABLES:
-        t[k] = torch.as_tensor(np.ascontiguousarray(host[k], dtype=np.float64 if dt == torch.float64 else np.int32)).to(device)
-    return t
+    def launch(C, C_out, out, src, grid):
+        (sr0, Hs, sc0, Ws), (H, W) = src, grid
+        ky, kx = (int(v) for v in t["k"])
+        check(lib().cra5_coarsen_f32(_p(x), C, Hs, Ws, sr0, sc0, H, W, 1 if (sc0 == 0 and Ws == W) else 0,
+                                     int(t["rows"][0]), ky, out.shape[1], int(t["cols"][0]), kx, out.shape[2], _p(t["row0"]),
+                                     _p(t["ntap"]), _p(t["rw"]), t["rw"].shape[1], _p(chan_map), C_out, _p(out), _stream()),
+              "cra5_coarsen_f32")
+    return _window_reduce("coarsen", x, t, out, chan_map, launch)
 
 
 def regrid(x, tables, out=None, chan_map=None):
@@ -753,46 +776,14 @@ def regrid(x, tables, out=None, chan_map=None):
     device).  chan_map: as in ops.coarsen.  The arithmetic is fixed (include/cra5_amd.h): bit-identical from run to run,
     and a sub-grid's result is the sub-block of the whole target grid's."""
     t = tables
-    _dev(x, out)
-    ok = isinstance(t, dict) and all(isinstance(t.get(k), torch.Tensor) and t[k].is_cuda and t[k].is_contiguous()
-                                     and t[k].dtype == dt for k, dt in _REGRID_TABLES)
-    if not ok:
-        raise ValueError("regrid: tables must come from ops.regrid_tables (row0 / ntap / order / col0 / ctap / tiles int32, "
-                         "rw / cw fp64 contiguous device tensors)")
-    Ho, Wo = int(t["Ho"]), int(t["Wo"])
-    sr0, sr1, sc0, snc = (int(v) for v in t["src_box"])
-    H, W = (int(v) for v in t["grid"])
-    if any(t[k].device != x.device for k, _ in _REGRID_TABLES):
-        raise ValueError(f"regrid: the tables are on {t['row0'].device}, x on {x.device}")
-    if (any(tuple(t[k].shape) != (Ho,) for k in ("row0", "ntap", "order")) or t["rw"].dim() != 2 or t["rw"].shape[0] != Ho
-            or any(tuple(t[k].shape) != (Wo,) for k in ("col0", "ctap")) or t["cw"].dim() != 2 or t["cw"].shape[0] != Wo
-            or t["tiles"].dim() != 2 or t["tiles"].shape[1] != 4 or t["tiles"].shape[0] < 1):
-        raise ValueError(f"regrid: the tables do not belong to a plan of {Ho} x {Wo} target points")
-    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous() or tuple(x.shape[1:]) != (sr1 - sr0, snc):
-        raise ValueError(f"regrid: x must be a contiguous fp32 [C, {sr1 - sr0}, {snc}] tensor - the plan's source box "
-                         f"{(sr0, sr1, sc0, snc)} (got {tuple(x.shape)} {x.dtype})")
-    C = x.shape[0]
-    if chan_map is not None:
-        if not (isinstance(chan_map, torch.Tensor) and chan_map.is_cuda and chan_map.dtype == torch.int32
-                and chan_map.dim() == 1 and chan_map.is_contiguous() and chan_map.numel() > 0
-                and chan_map.device == x.device):
-            raise ValueError("regrid: chan_map must be a contiguous int32 vector on x's device")
-        C_out = chan_map.numel()
-    else:
-        C_out = C
-    if out is None:
-        out = torch.empty((C_out, Ho, Wo), device=x.device, dtype=torch.float32)
-    if not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (C_out, Ho, Wo)
-            and out.device == x.device):
-        raise ValueError(f"regrid: out must be a contiguous fp32 [{C_out}, {Ho}, {Wo}] tensor on x's device")
-    ev = TIMER.start() if TIMER is not None else None
-    check(lib().cra5_regrid_f32(_p(x), C, sr1 - sr0, snc, sr0, sc0, H, W, Ho, Wo, _p(t["row0"]), _p(t["ntap"]), _p(t["rw"]),
-                                t["rw"].shape[1], _p(t["order"]), _p(t["col0"]), _p(t["ctap"]), _p(t["cw"]),
-                                t["cw"].shape[1], _p(t["tiles"]), t["tiles"].shape[0], int(t["tile_cols"]),
-                                int(t["max_span"]), _p(chan_map), C_out, _p(out), _stream()), "cra5_regrid_f32")
-    if ev is not None:
-        TIMER.stop("regrid", ev, 4.0 * (C_out * (sr1 - sr0) * snc + C_out * Ho * Wo))
-    return out
+
+    def launch(C, C_out, out, src, grid):
+        (sr0, Hs, sc0, Ws), (H, W) = src, grid
+        check(lib().cra5_regrid_f32(_p(x), C, Hs, Ws, sr0, sc0, H, W, out.shape[1], out.shape[2], _p(t["row0"]), _p(t["ntap"]),
+                                    _p(t["rw"]), t["rw"].shape[1], _p(t["order"]), _p(t["col0"]), _p(t["ctap"]), _p(t["cw"]),
+                                    t["cw"].shape[1], _p(t["tiles"]), t["tiles"].shape[0], int(t["tile_cols"]),
+                                    int(t["max_span"]), _p(chan_map), C_out, _p(out), _stream()), "cra5_regrid_f32")
+    return _window_reduce("regrid", x, t, out, chan_map, launch)
 
 
 PROBE_PARTIALS = 256     # CRA5_PROBE_PARTIALS

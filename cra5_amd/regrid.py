@@ -1,4 +1,4 @@
-"""Regridding onto any rectilinear lat/lon grid: the host-side geometry of cra5_regrid_f32 (csrc/regrid.hip; DESIGN.md
+"""Regridding onto any rectilinear lat/lon grid: the host-side geometry of cra5_regrid_f32 (csrc/window_reduce.hip; DESIGN.md
 section 4, "Regridding").  numpy only - no model, no GPU.
 
 `Grid` is a target grid (cell centres, optional cell bounds, a method); `Grid.plan(H, W)` turns it into the separable
@@ -23,7 +23,7 @@ import numpy as np
 from .subset import TOL_DEG, _edge_lat
 
 METHODS = ("bilinear", "conservative")
-# the kernel's LDS budget (csrc/regrid.hip): one staged source row of a tile, and the tile's column weights
+# the kernel's LDS budget (csrc/window_reduce.hip): one staged source row of a tile, and the tile's column weights
 SPAN_MAX = 7936            # floats of one staged row
 CW_LDS_DOUBLES = 4096      # tile columns x cw pitch
 MAX_TILE_COLS = 256

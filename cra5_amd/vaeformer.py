@@ -794,8 +794,8 @@ class VAEformer(nn.Module):
         """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300).  channels / box / step (canonical, _subset_args):
         the [len(channels), r1 - r0, nc] slice of that frame - thinned to the global rows % s_lat == 0 / columns % s_lon
         == 0 when step = (s_lat, s_lon) -, bit for bit (_unembed).  coarsen = (k_lat, k_lon) (_coarsen_arg; not with a
-        step): the area-weighted mean of that frame at the points step = coarsen would keep (_unembed_coarsened).  regrid (a
-        plan, _regrid_arg; on its own): that frame on the plan's target grid (_unembed_regridded).  out: the
+        step): the area-weighted mean of that frame at the points step = coarsen would keep (_unembed_windowed).  regrid (a
+        plan, _regrid_arg; on its own): that frame on the plan's target grid (_unembed_windowed).  out: the
         contiguous destination of _decoded_shape (one frame of the caller's batch result) - the un-embed writes x_hat
         there; None: a fresh tensor."""
         cfg = self.cfg
@@ -891,6 +891,17 @@ class VAEformer(nn.Module):
         """ops.regrid_tables of a canonical plan - built once per target grid, cached like the coarsening tables."""
         return self._sub_cached(("rplan", self.device, plan["key"]), self, lambda: ops.regrid_tables(plan, self.device))
 
+    def _window_frame(self, name, x, plan, tdev, op, out):
+        """coarsen_frame / regrid_frame (`name`): the whole frame x [C, H, W], cropped to the plan's source box when that
+        is not the whole grid, through op (ops.coarsen | ops.regrid) with the plan's device tables."""
+        H, W = self.cfg['img_size']
+        if x.dim() != 3 or tuple(x.shape[1:]) != (H, W):
+            raise ValueError(f"{name}: x must be a [C, {H}, {W}] frame, got {tuple(x.shape)}")
+        sr0, sr1, sc0, snc = plan["src_box"]
+        if (sr0, sr1, sc0, snc) != (0, H, 0, W):
+            x = ops.crop(x, sr0, sr1 - sr0, sc0, snc, out=self._buf(name + "_src", (x.shape[0], sr1 - sr0, snc)))
+        return op(x, tdev, out=out)
+
     def regrid_frame(self, x, grid, out=None):
         """A whole frame x [C, H, W] (contiguous fp32, on the model's device) on the target grid (regrid.Grid | its plan)
         -> [C, Ho, Wo]: what a decode with regrid= returns, applied to a frame already on the device (the truth frame of
@@ -899,13 +910,7 @@ class VAEformer(nn.Module):
         plan = self._regrid_arg(grid)
         if plan is None:
             raise ValueError("regrid_frame: grid must be a regrid.Grid or its plan")
-        H, W = self.cfg['img_size']
-        if x.dim() != 3 or tuple(x.shape[1:]) != (H, W):
-            raise ValueError(f"regrid_frame: x must be a [C, {H}, {W}] frame, got {tuple(x.shape)}")
-        sr0, sr1, sc0, snc = plan["src_box"]
-        if (sr0, sr1, sc0, snc) != (0, H, 0, W):
-            x = ops.crop(x, sr0, sr1 - sr0, sc0, snc, out=self._buf("regrid_frame_src", (x.shape[0], sr1 - sr0, snc)))
-        return ops.regrid(x, self._regrid_tables(plan), out=out)
+        return self._window_frame("regrid_frame", x, plan, self._regrid_tables(plan), ops.regrid, out)
 
     def _coarsen_tables(self, box, k):
         """(subset.coarsen_plan, ops.coarsen_tables) of the canonical box and factor - built once per (box, k), cached
@@ -925,7 +930,7 @@ class VAEformer(nn.Module):
         k = self._coarsen_arg(coarsen, None)
         if k is None:
             raise ValueError("coarsen_frame: coarsen must be a factor > 1 in at least one dimension")
-        return ops.coarsen(x, self._coarsen_tables(None, k)[1], out=out)
+        return self._window_frame("coarsen_frame", x, *self._coarsen_tables(None, k), ops.coarsen, out)
 
     def _sub_cached(self, key, src, make):
         """Entry `key` of the bounded subset cache, rebuilt by `make()` when `src` (the tensor / derived weight it was
@@ -1007,11 +1012,11 @@ class VAEformer(nn.Module):
         into `out` (_frame_dest: a frame of the caller's batch result - every form below stores straight into it; None:
         a fresh tensor).  chans = box = None is the full decode.  step = (s_lat, s_lon): only the box's points on the
         global lattice rows % s_lat == 0, columns % s_lon == 0 -> [C', Ho, Wo] (_unembed_thinned: the same products, far
-        fewer).  coarsen = (k_lat, k_lon): _unembed_coarsened.  regrid (a plan): _unembed_regridded."""
+        fewer).  coarsen = (k_lat, k_lon) / regrid (a plan): _unembed_windowed with that plan and its operator."""
         if regrid is not None:
-            return self._unembed_regridded(h, mean, std, chans, regrid, out)
+            return self._unembed_windowed(h, mean, std, chans, regrid, self._regrid_tables(regrid), ops.regrid, "ue_regrid_src", out)
         if coarsen is not None:
-            return self._unembed_coarsened(h, mean, std, chans, box, coarsen, out)
+            return self._unembed_windowed(h, mean, std, chans, *self._coarsen_tables(box, coarsen), ops.coarsen, "ue_coarse_src", out)
         if step is not None:
             return self._unembed_thinned(h, mean, std, chans, box, step, out)
         cfg = self.cfg
@@ -1148,37 +1153,23 @@ class VAEformer(nn.Module):
         out = self._frame_dest(out, (Cs, p["Ho"], p["Wo"]))
         return ops.strided_scatter(g, tdev["rows"], tdev["cols"], tdev["cls"], tb["n_cc"], Cs, mean=ms, std=ss, out=out)
 
-    def _unembed_coarsened(self, h, mean, std, chans, box, k, out=None):
-        """_unembed with a coarsening factor k = (k_lat, k_lon): the un-embed runs unthinned on the source box the
-        windows need (subset.coarsen_plan: the box's kept points grown by k // 2 rows / columns, the whole circle when it
-        closes) into a per-thread persistent buffer - de-normalised when mean / std are given: x * std + mean is affine
-        per channel, so the weighted mean of the de-normalised values IS what coarsening the full decode returns - and
-        ONE streaming kernel (ops.coarsen, csrc/coarsen.hip) writes the area-weighted means into `out`.  The source
+    def _unembed_windowed(self, h, mean, std, chans, plan, tdev, op, buf, out=None):
+        """_unembed through a windowed reduction: coarsen = (k_lat, k_lon) (plan, tdev = _coarsen_tables(box, k), op =
+        ops.coarsen) or a target grid (a canonical plan of _regrid_arg, tdev = _regrid_tables(plan), op = ops.regrid).
+        The un-embed runs unthinned on the source box the plan's windows need (subset.coarsen_plan: the box's kept points
+        grown by k // 2 rows / columns; Grid.plan: the hull of all taps; the whole circle when it closes) into the
+        per-thread persistent buffer `buf` - one per operator: a thread that alternates the two keeps both workspaces -,
+        de-normalised when mean / std are given: x * std + mean is affine per channel and the weights of a row and of a
+        column sum to 1 (up to rounding), so the weighted mean of the de-normalised values IS what the operator returns on
+        the full decode - and ONE streaming kernel (csrc/window_reduce.hip) writes the result into `out`.  The source
         buffer holds exactly the values (bits) the full decode has there (_unembed: the subset decode's guarantee)."""
         H, W = self.cfg['img_size']
-        plan, tdev = self._coarsen_tables(box, k)
         sb = tuple(int(v) for v in plan["src_box"])
         Cs = len(chans) if chans is not None else self.cfg['out_chans']
-        src = self._buf("ue_coarse_src", (Cs, sb[1] - sb[0], sb[3]))
+        src = self._buf(buf, (Cs, sb[1] - sb[0], sb[3]))
         self._unembed(h, mean, std, chans, None if sb == (0, H, 0, W) else sb, None, out=src)
         out = self._frame_dest(out, (Cs, plan["Ho"], plan["Wo"]))
-        return ops.coarsen(src, tdev, out=out)
-
-    def _unembed_regridded(self, h, mean, std, chans, plan, out=None):
-        """_unembed onto a target grid (a canonical plan of _regrid_arg), on the pattern of _unembed_coarsened: the
-        un-embed runs on the source box the plan's windows need - the hull of all taps, the whole circle when it closes -
-        into a per-thread persistent buffer, de-normalised when mean / std are given (the weights of a row and of a
-        column sum to 1 up to rounding, x * std + mean is affine per channel), and ONE streaming kernel (ops.regrid,
-        csrc/regrid.hip) writes the target grid into `out`.  The source buffer holds exactly the values (bits) the full
-        decode has there."""
-        H, W = self.cfg['img_size']
-        tdev = self._regrid_tables(plan)
-        sb = tuple(int(v) for v in plan["src_box"])
-        Cs = len(chans) if chans is not None else self.cfg['out_chans']
-        src = self._buf("ue_regrid_src", (Cs, sb[1] - sb[0], sb[3]))
-        self._unembed(h, mean, std, chans, None if sb == (0, H, 0, W) else sb, None, out=src)
-        out = self._frame_dest(out, (Cs, plan["Ho"], plan["Wo"]))
-        return ops.regrid(src, tdev, out=out)
+        return op(src, tdev, out=out)
 
     # ---- latent side: everything between y and the entropy coder ---------------------------
     def _latent_side_frame(self, y, want_lik=False, z_sym_out=None):

@@ -302,7 +302,7 @@ int cra5_strided_scatter_f32(const float *g, size_t g_elems, const int *rows, co
                              int n_rc, int n_cc, const float *mean, const float *stdv, float *x, int C, int Ho, int Wo,
                              void *stream);
 
-/* Area-weighted coarsening (csrc/coarsen.hip; cra5_amd/subset.py coarsen_plan): the first-order
+/* Area-weighted coarsening (csrc/window_reduce.hip; cra5_amd/subset.py coarsen_plan): the first-order
  * conservative regrid of src - fp32 [C_src][Hs][Ws], contiguous, whose element [.][0][0] is the GLOBAL grid point (src_r0,
  * src_c0) of an H x W grid; whole_circle != 0: Ws == W and src_c0 == 0, windows wrap at the east edge - onto the Ho x Wo
  * points of global rows out_r0 + i * k_lat and global columns (out_c0 + j * k_lon) mod W -> dst fp32 [C_out][Ho][Wo],
@@ -323,7 +323,7 @@ int cra5_coarsen_f32(const float *src, int C_src, int Hs, int Ws, int src_r0, in
                      int out_r0, int k_lat, int Ho, int out_c0, int k_lon, int Wo, const int *row0, const int *ntap,
                      const double *rw, int rw_pitch, const int *chan_map, int C_out, float *dst, void *stream);
 
-/* Regridding onto any rectilinear lat/lon grid (csrc/regrid.hip; cra5_amd/regrid.py Grid.plan):
+/* Regridding onto any rectilinear lat/lon grid (csrc/window_reduce.hip; cra5_amd/regrid.py Grid.plan):
  * bilinear interpolation or first-order conservative remapping of src - fp32 [C_src][Hs][Ws], contiguous, whose element
  * [.][0][0] is the GLOBAL grid point (src_r0, src_c0) of an H x W grid; Ws == W: the whole circle, src_c0 == 0, windows
  * wrap at the east edge - onto Ho x Wo target points -> dst fp32 [C_out][Ho][Wo], contiguous.  chan_map: as in

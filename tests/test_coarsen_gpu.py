@@ -122,6 +122,53 @@ def test_kernel_chan_map_alignment_nonfinite_and_sub_block(dev):
             assert np.array_equal(sub.view(np.int32), glob[:, ii][:, :, jj].view(np.int32)), (kk, box)
 
 
+def _launch_rows(C_out, n_tiles, Ho):
+    """(rows_per_block, n_chunks) of a launch: the launcher's rule - at least 4096 blocks, at most one chunk per row."""
+    chunks = max(1, min(Ho, -(-4096 // (C_out * n_tiles))))
+    rpb = -(-Ho // chunks)
+    return rpb, -(-Ho // rpb)
+
+
+def _n_tiles(Wo, k_lon):
+    tc = min((256 * 8 * 4 - 16 - 2 * (k_lon // 2) - 1) // k_lon + 1, 256, Wo)
+    return -(-Wo // tc)
+
+
+# (grid, k, C_out, box index of _boxes, (Ho, Wo), column tiles, rows per block, chunks)
+WALKS = [((25, 40), (4, 4), 2048, 0, (7, 10), 1, 4, 2),
+         ((25, 40), (2, 2), 1024, 0, (13, 20), 1, 4, 4),
+         ((25, 40), (3, 8), 1024, 0, (9, 5), 1, 3, 3),            # odd k_lat: no shared rows
+         ((25, 40), (12, 8), 2048, 0, (3, 5), 1, 2, 2),           # 13-row windows
+         ((7, 1440), (2, 2), 1400, 0, (4, 720), 3, 4, 1),         # three column tiles, the east-edge second piece
+         ((25, 40), (4, 4), 2048, 4, (5, 3), 1, 3, 2)]            # a region across 0 deg
+
+
+@pytest.mark.parametrize("case", WALKS, ids=lambda c: f"{c[0][0]}x{c[0][1]}-k{c[1][0]}x{c[1][1]}-C{c[2]}-box{c[3]}")
+def test_kernel_walks_runs_of_rows_per_block(dev, case):
+    """A long chan_map over a 3-channel source: C_out * tiles is large enough that one block walks several output rows -
+    the carried inner of a shared edge row, the look-ahead load, the chunk boundary where a shared row is read again."""
+    (Hg, Wg), k, C_out, b, shape, tiles, rpb, chunks = case
+    full = _field(3, Hg, Wg, seed=Hg + k[0])
+    box = _boxes(Hg, Wg, k)[b]
+    cmap = ((np.arange(C_out) * 7 + 1) % 3).tolist()
+    plan = subset.coarsen_plan(box, k, Hg, Wg)
+    assert (plan["Ho"], plan["Wo"]) == shape and _n_tiles(plan["Wo"], k[1]) == tiles
+    assert _launch_rows(C_out, tiles, plan["Ho"]) == (rpb, chunks) and rpb > 1
+    ref = ch.ref_coarsen(full, k, box)
+    assert _same_bits(_run(full, k, box, dev, chan_map=cmap), ref[cmap])
+    if case is WALKS[0]:
+        # the source 4 bytes off a 16-byte boundary
+        assert _same_bits(_run(full, k, box, dev, chan_map=cmap, off_src=1), ref[cmap])
+        # a NaN in source row 6: the edge row that output rows 1 and 2 - both in block 0's run - share
+        bad = full.copy()
+        bad[1, 6, 10] = np.nan
+        ref = ch.ref_coarsen(bad, k, box)
+        got = _run(bad, k, box, dev, chan_map=cmap)
+        assert np.array_equal(got, ref[cmap], equal_nan=True)
+        where = np.argwhere(np.isnan(ref[1]))
+        assert sorted(set(where[:, 0].tolist())) == [1, 2] and len(where) == 4 and not np.isnan(ref[[0, 2]]).any()
+
+
 def test_ops_argument_checks(dev):
     Hg, Wg, k = 13, 24, (6, 6)
     full = _field(2, Hg, Wg, seed=1)

@@ -131,6 +131,41 @@ def test_kernel_chan_map_alignment_nonfinite_and_sub_block(dev):
             assert np.array_equal(got.view(np.int32), glob[:, a:b, c:d].view(np.int32)), (m, a, b, c, d)
 
 
+def _launch_rows(C_out, n_tiles, Ho):
+    """(rows_per_block, n_chunks) of a launch: the launcher's rule - at least 4096 blocks, at most one chunk per row."""
+    chunks = max(1, min(Ho, -(-4096 // (C_out * n_tiles))))
+    rpb = -(-Ho // chunks)
+    return rpb, -(-Ho // rpb)
+
+
+WALK_LAT, WALK_LON = 88.0 - 8.0 * np.arange(22), 2.0 + 12.0 * np.arange(30)
+# (target grid, C_out, Ho, rows per block, chunks)
+WALKS = {"bilinear": (Grid(WALK_LAT, WALK_LON, "bilinear"), 1024, 22, 6, 4),
+         "bilinear south-to-north": (Grid(WALK_LAT[::-1].copy(), WALK_LON, "bilinear"), 1024, 22, 6, 4),     # through `order`
+         "conservative south-to-north": (Grid(WALK_LAT[::-1].copy(), WALK_LON, "conservative"), 1024, 22, 6, 4),   # 3 x 3 taps
+         "5 x 5 taps": (Grid.equiangular(6, 12, method="conservative"), 2048, 6, 3, 2)}       # windows sharing edge rows
+
+
+def test_kernel_walks_runs_of_rows_per_block(dev):
+    """A long chan_map over a 3-channel source: C_out * tiles is large enough that one block walks several target rows -
+    the two kept inner, the look-ahead load, `order`, the chunk boundary where a shared row is staged again."""
+    Hg, Wg = 25, 40
+    full = rh.field(3, Hg, Wg, seed=21)
+    got = {}
+    for name, (g, C_out, Ho, rpb, chunks) in WALKS.items():
+        plan = g.plan(Hg, Wg)
+        cmap = ((np.arange(C_out) * 7 + 1) % 3).tolist()
+        assert plan["Ho"] == Ho and len(tile_table(plan)[0]) == 1
+        assert _launch_rows(C_out, 1, Ho) == (rpb, chunks) and rpb > 1 and _launch_rows(3, 1, Ho) == (1, Ho)
+        got[name] = _run(full, plan, dev, chan_map=cmap)
+        assert same_bits(got[name], ref_regrid(full, plan)[0][cmap]), name
+        # the plain 3-channel source walks one row per block: the multi-row walk against the single-row walk
+        assert same_bits(got[name], _run(full, plan, dev)[cmap]), name
+    assert int(WALKS["conservative south-to-north"][0].plan(Hg, Wg)["ntap"].max()) == 3
+    assert int(WALKS["5 x 5 taps"][0].plan(Hg, Wg)["ntap"].max()) == 5
+    assert same_bits(got["bilinear south-to-north"], got["bilinear"][:, ::-1])
+
+
 def test_ops_argument_checks(dev):
     Hg, Wg = 13, 24
     full = rh.field(2, Hg, Wg, seed=1)

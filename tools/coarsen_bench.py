@@ -1,4 +1,4 @@
-"""Area-weighted coarsening (csrc/coarsen.hip, coarsen= of cra5_api): kernel time and HBM rate of cra5_coarsen_f32 on a
+"""Area-weighted coarsening (csrc/window_reduce.hip, coarsen= of cra5_api): kernel time and HBM rate of cra5_coarsen_f32 on a
 268 x 721 x 1440 frame at k = 2, 6 and 24 - beside this project's own streaming yardsticks on the same box in the same
 run, the overlap-add (csrc/elementwise.hip), the reconstruction-error kernel (csrc/metrics.hip) and the time-statistics
 accumulate (csrc/timestats.hip); below half of the overlap-add's rate the report says which limit was hit -, then
@@ -116,7 +116,7 @@ def sweep(dev, n, workers, reps):
 
 def _row_steps(Ho, Wo, k):
     """(block, source row) steps of one launch on the whole frame and the floats one step stages - the launcher's tiling
-    (csrc/coarsen.hip): tiles of <= 256 output columns, >= 4096 blocks, a shared edge row read again per run of rows."""
+    (csrc/window_reduce.hip): tiles of <= 256 output columns, >= 4096 blocks, a shared edge row read again per run of rows."""
     span_max = 256 * 8 * 4 - 16
     tc = min((span_max - 2 * (k // 2) - 1) // k + 1, 256, Wo)
     n_tiles = -(-Wo // tc)

@@ -1,4 +1,4 @@
-"""Regridding (csrc/regrid.hip, regrid= of cra5_api): kernel time and HBM rate of cra5_regrid_f32 on a 268 x 721 x 1440
+"""Regridding (csrc/window_reduce.hip, regrid= of cra5_api): kernel time and HBM rate of cra5_regrid_f32 on a 268 x 721 x 1440
 frame for three targets -
   (a) conservative onto coarsen=6's own 121 x 240 cells (bounds from grid_box(coarsen=6)), beside ops.coarsen on that grid;
   (b) conservative onto the 128 x 256 equiangular grid;
@@ -65,7 +65,7 @@ def _dense(plan):
 
 
 def _steps(plan, tiles):
-    """(block, staged source row) steps of one launch on the whole frame - the launcher's chunks (csrc/regrid.hip): >= 4096
+    """(block, staged source row) steps of one launch on the whole frame - the launcher's chunks (csrc/window_reduce.hip): >= 4096
     blocks; a block stages every source row of its run of target rows once (the two kept inner), the rows two runs
     share again."""
     n_tiles = len(tiles)
