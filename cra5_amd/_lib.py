@@ -45,6 +45,7 @@ SIGNATURES = {
                                  c_int, c_int, c_int, c_void_p]),
     "cra5_gemm_nt_split": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                    c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "cra5_gemm_split_form": (c_int, [c_int] * 6),
     "cra5_split_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "cra5_layernorm_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                    c_int, c_float, c_int, c_void_p]),

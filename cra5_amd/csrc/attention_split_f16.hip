@@ -977,7 +977,7 @@ int launch(const unsigned short *qkv, long ldq, const unsigned short *pad_row, f
 
 static int attention_dispatch(const uint16_t *qkv_split, int qkv_kp, const uint16_t *pad_row_split, float *out,
                               uint16_t *out_split, int out_kp, int C, int heads, int H, int W, int wh, int ww,
-                              float scale, int hi_only, void *workspace, size_t workspace_bytes, void *stream,
+                              float scale, int mode, void *workspace, size_t workspace_bytes, void *stream,
                               bool want_balanced) {
   if (!qkv_split || !pad_row_split || (!out && !out_split) || heads <= 0 || C % heads) return CRA5_ERR_ARG;
   if (C / heads != 64 || qkv_kp != 3 * C) return CRA5_ERR_ARG;  // head slices must be chunk-aligned
@@ -986,10 +986,12 @@ static int attention_dispatch(const uint16_t *qkv_split, int qkv_kp, const uint1
   if (((uintptr_t)qkv_split & 15) || ((uintptr_t)pad_row_split & 15)) return CRA5_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int L = wh * ww;
-  // hi_only: 0 = fp32-accurate, 1 = reduced precision on split rows, 3 = reduced precision on PLAIN f16 rows (qkv, the
-  // pad row and out_split: element n at half n; row pitches unchanged).
-  if (hi_only != 0 && hi_only != 1 && hi_only != 3) return CRA5_ERR_ARG;
-  const bool plain = hi_only == 3;
+  // mode (the CRA5_GEMM_* word): 0 = fp32-accurate, HI_ONLY = reduced precision on split rows, HI_ONLY | A_PLAIN |
+  // OUT_PLAIN = reduced precision on PLAIN f16 rows (qkv, the pad row and out_split: element n at half n; row pitches
+  // unchanged).
+  constexpr int PLAIN_ROWS = CRA5_GEMM_HI_ONLY | CRA5_GEMM_A_PLAIN | CRA5_GEMM_OUT_PLAIN;
+  if (mode != 0 && mode != CRA5_GEMM_HI_ONLY && mode != PLAIN_ROWS) return CRA5_ERR_ARG;
+  const bool hi_only = mode != 0, plain = mode == PLAIN_ROWS;
   const long ldq = 2L * qkv_kp;
   const bool whole = (wh == H && ww == W);
   if (!whole && L > MAX_WIN_TOKENS) return CRA5_ERR_ARG;   // attention_f32.hip covers those
@@ -1039,9 +1041,9 @@ extern "C" int cra5_debug_attn_trace(unsigned long long *host, int n_rows) {
 
 extern "C" int cra5_window_attention_split(const uint16_t *qkv_split, int qkv_kp, const uint16_t *pad_row_split,
                                            float *out, uint16_t *out_split, int out_kp, int C, int heads, int H,
-                                           int W, int wh, int ww, float scale, int hi_only, void *stream) {
+                                           int W, int wh, int ww, float scale, int mode, void *stream) {
   return attention_dispatch(qkv_split, qkv_kp, pad_row_split, out, out_split, out_kp, C, heads, H, W, wh, ww, scale,
-                            hi_only, nullptr, 0, stream, false);
+                            mode, nullptr, 0, stream, false);
 }
 
 extern "C" size_t cra5_attention_workspace_bytes(int n_tokens, int heads) {
@@ -1052,10 +1054,10 @@ extern "C" size_t cra5_attention_workspace_bytes(int n_tokens, int heads) {
 
 extern "C" int cra5_window_attention_split_ws(const uint16_t *qkv_split, int qkv_kp, const uint16_t *pad_row_split,
                                               float *out, uint16_t *out_split, int out_kp, int C, int heads, int H,
-                                              int W, int wh, int ww, float scale, int hi_only, void *workspace,
+                                              int W, int wh, int ww, float scale, int mode, void *workspace,
                                               size_t workspace_bytes, void *stream) {
   return attention_dispatch(qkv_split, qkv_kp, pad_row_split, out, out_split, out_kp, C, heads, H, W, wh, ww, scale,
-                            hi_only, workspace, workspace_bytes, stream, true);
+                            mode, workspace, workspace_bytes, stream, true);
 }
 
 extern "C" int cra5_attention_balanced_plan(int n_tokens, int heads, size_t *workspace_bytes) {

@@ -569,66 +569,75 @@ __global__ __launch_bounds__(256) void unembed_fixup_kernel(const float *__restr
 
 }  // namespace
 
-static int gemm_dispatch(const unsigned short *A, long lda, const unsigned short *W, long ldw, float *C, int ldc,
+// THE form rule of cra5_gemm_nt_split (include/cra5_amd.h): which tile, which k-step, chained or not, plain rows or not -
+// or CRA5_ERR_ARG.  Host arithmetic only; gemm_dispatch launches what it answers.
+extern "C" int cra5_gemm_split_form(int M, int N, int Kp, int flags, int has_f32_out, int has_split_out) {
+  if ((!has_f32_out && !has_split_out) || M <= 0 || N <= 0 || Kp <= 0 || (Kp % BK)) return CRA5_ERR_ARG;
+  const bool hi = flags & CRA5_GEMM_HI_ONLY, force_wide = flags & CRA5_GEMM_WIDE_K;
+  const bool plain = flags & (CRA5_GEMM_A_PLAIN | CRA5_GEMM_W_PLAIN | CRA5_GEMM_OUT_PLAIN);
+  // Long reductions (patch-embed conv, K = 29 480): K is cut into chunks of <= 8192 whose partial products are chained
+  // through the fp32 C matrix (C += A_i . W_i): a two-level sum (each chunk accumulates in the MFMA accumulators, chunks
+  // add in fp32) without a second accumulator register set, so the big tiles stay spill-free.  A split output or a GELU
+  // cannot be chained: those run the one-launch long-K kernel.
+  const bool chained = Kp > 8192 && has_f32_out && !has_split_out && !(flags & CRA5_EPI_GELU);
+  const bool longk = Kp > 8192 && !chained;
+  const bool big = (long)((M + 127) / 128) * ((N + 127) / 128) >= 256;
+  // the wide reduced-precision form: 64 k-values (the hi halves of two chunks) per k-step, the fp32-accurate mode's loop.
+  // CRA5_GEMM_WIDE_K asks for it at any size (a slice of a big launch, same summation order) and is refused where it
+  // cannot hold; plain-f16 operands / output exist in this form only (the caller falls back to split rows)
+  const bool k64 = hi && !longk && Kp % 64 == 0 && (big || force_wide);
+  if ((force_wide && (!k64 || chained)) || (plain && !k64)) return CRA5_ERR_ARG;
+  // measured on MI355X (tools/gemm_bench.py, M = 10368): N = 1024 (proj, fc2, patch-embed): 192x256 tiles = 216 blocks,
+  // one round on 256 CUs; N >= 3072: 256x256 tiles.  < 256 128 x 128 tiles: 64 x 64 tiles (launch-bound sizes).
+  // (a 4-wave 256 x 256 instantiation - one wave per SIMD, 128 x 128 per wave, 256 accumulator AGPRs, a third less
+  // LDS fragment traffic per MFMA - compiles spill-free but measured 4-5 % SLOWER with hipcc's schedule: qkv 197 vs
+  // 190 us, un-embed 1922 vs 1832; a single wave per SIMD needs a hand-placed MFMA / ds_read / LDS-DMA interleave)
+  int tile = 128;   // the one-launch long-K kernel's, and the fp32-accurate mode's for a narrow big problem
+  if (!longk) {
+    if (!big && !force_wide) tile = 64;
+    else if (M >= 1024 && N >= 2048) tile = 256;
+    else if (hi || (M >= 1024 && N >= 512)) tile = 192;   // (the reduced-precision mode has no 128-row big tile)
+  }
+  return tile | (k64 ? CRA5_FORM_K64 : 0) | (chained ? CRA5_FORM_CHAINED : 0) | (plain ? CRA5_FORM_PLAIN : 0);
+}
+
+// One launch (a whole call, or one chunk of a chained one) in the form cra5_gemm_split_form gave for the call.
+static int gemm_dispatch(int form, const unsigned short *A, long lda, const unsigned short *W, long ldw, float *C, int ldc,
                          unsigned short *C_split, long ldcs, const float *bias, const float *res, int ldr, int M,
                          int N, int Kp, float wscale_inv, int flags, hipStream_t st) {
-  const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-#define CRA5_GO(WM, WN, TM, TN, LK) \
-  return launch<WM, WN, TM, TN, LK>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st)
+#define CRA5_GO(WM, WN, TM, TN, LK, NP) \
+  return launch<WM, WN, TM, TN, LK, NP>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st)
+  int tile = form & CRA5_FORM_TILE;
+  if (Kp > 8192) CRA5_GO(2, 2, 2, 2, true, 3);
+  if (flags & CRA5_GEMM_HI_ONLY) {   // reduced precision: one f16 MFMA per product
+    if (tile == 64) CRA5_GO(2, 2, 1, 1, false, 1);
+    if (form & CRA5_FORM_K64) {
+      if (tile == 256) CRA5_GO(2, 4, 4, 2, false, 2);
+      CRA5_GO(2, 4, 3, 2, false, 2);
+    }
+    if (tile == 256) CRA5_GO(2, 4, 4, 2, false, 1);
+    CRA5_GO(2, 4, 3, 2, false, 1);
+  }
 // trace build only (tools/gemm_trace.py --active forces a tile): the product library reads no environment variable
 #ifdef CRA5_GEMM_TRACE
   static const int forced = [] {
     const char *e = getenv("CRA5_GEMM_TILE");
     return e ? atoi(e) : 0;
   }();
-#else
-  constexpr int forced = 0;
+  if (forced) tile = forced;
 #endif
-  const bool longk = Kp > 8192;
-  // CRA5_GEMM_WIDE_K: the wide reduced-precision form at any size (a slice of a big launch, same summation order)
-  const bool force_wide = flags & CRA5_GEMM_WIDE_K;
-  if (force_wide && (!(flags & CRA5_GEMM_HI_ONLY) || longk || (Kp % 64))) return CRA5_ERR_ARG;
-  // plain-f16 operands / output exist in the wide reduced-precision form only (the caller falls back to split rows)
-  constexpr int PLAIN_ANY = CRA5_GEMM_A_PLAIN | CRA5_GEMM_W_PLAIN | CRA5_GEMM_OUT_PLAIN;
-  if ((flags & PLAIN_ANY) && (!(flags & CRA5_GEMM_HI_ONLY) || longk || (tiles128 < 256 && !force_wide) || (Kp % 64)))
-    return CRA5_ERR_ARG;
-  if (longk) CRA5_GO(2, 2, 2, 2, true);
-  if (flags & CRA5_GEMM_HI_ONLY) {   // reduced precision: one f16 MFMA per product
-    const bool wide = (M >= 1024 && N >= 2048);
-    if (tiles128 < 256 && !force_wide)
-      return launch<2, 2, 1, 1, false, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
-    if (Kp % 64 == 0) {   // wide form: 64 k-values (the hi halves of two chunks) per k-step, the fp32-accurate mode's loop
-      if (wide)
-        return launch<2, 4, 4, 2, false, 2>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
-      return launch<2, 4, 3, 2, false, 2>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
-    }
-    if (wide)
-      return launch<2, 4, 4, 2, false, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
-    return launch<2, 4, 3, 2, false, 1>(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
-  }
-  int tile = forced;
-  if (!tile) {
-    // measured on MI355X (tools/gemm_bench.py, M = 10368): N = 1024 (proj, fc2, patch-embed):
-    // 192x256 tiles = 216 blocks, one round on 256 CUs; N >= 3072: 256x256 tiles.
-    if (tiles128 < 256) tile = 64;
-    else if (M >= 1024 && N >= 2048) tile = 256;
-    else if (M >= 1024 && N >= 512) tile = 192;
-    else tile = 128;
-  }
-  // (a 4-wave 256 x 256 instantiation - one wave per SIMD, 128 x 128 per wave, 256 accumulator AGPRs, a third less
-  // LDS fragment traffic per MFMA - compiles spill-free but measured 4-5 % SLOWER with hipcc's schedule: qkv 197 vs
-  // 190 us, un-embed 1922 vs 1832; a single wave per SIMD needs a hand-placed MFMA / ds_read / LDS-DMA interleave)
-  if (tile == 64) CRA5_GO(2, 2, 1, 1, false);
-  if (tile == 192) CRA5_GO(2, 4, 3, 2, false);   // 192 x 256, 8 waves (2 x 4), 3 x 2 sub-tiles per wave
-  if (tile == 256) CRA5_GO(2, 4, 4, 2, false);   // 256 x 256, 8 waves (2 x 4), 4 x 2 sub-tiles per wave
-  CRA5_GO(2, 2, 2, 2, false);
+  if (tile == 64) CRA5_GO(2, 2, 1, 1, false, 3);
+  if (tile == 192) CRA5_GO(2, 4, 3, 2, false, 3);   // 192 x 256, 8 waves (2 x 4), 3 x 2 sub-tiles per wave
+  if (tile == 256) CRA5_GO(2, 4, 4, 2, false, 3);   // 256 x 256, 8 waves (2 x 4), 4 x 2 sub-tiles per wave
+  CRA5_GO(2, 2, 2, 2, false, 3);
 #undef CRA5_GO
 }
 
 extern "C" int cra5_gemm_nt_split(const uint16_t *A, int lda_kp, const uint16_t *W, int ldw_kp, float *C, int ldc,
                                   uint16_t *C_split, int ldc_split_kp, const float *bias, const float *res, int ldr,
                                   int M, int N, int Kp, float wscale_inv, int flags, void *stream) {
-  if (!A || !W || (!C && !C_split) || M <= 0 || N <= 0 || Kp <= 0 || (Kp % BK)) return CRA5_ERR_ARG;
+  const int form = cra5_gemm_split_form(M, N, Kp, flags, C != nullptr, C_split != nullptr);
+  if (!A || !W || form < 0) return CRA5_ERR_ARG;
   if (lda_kp < Kp || ldw_kp < Kp || (lda_kp % 32) || (ldw_kp % 32)) return CRA5_ERR_ARG;
   if (lda_kp >= (1 << 21) || ldw_kp >= (1 << 21)) return CRA5_ERR_ARG;   // 32-bit tile-relative DMA offsets (2 halves per k)
   if (((uintptr_t)A & 15) || ((uintptr_t)W & 15)) return CRA5_ERR_ARG;
@@ -640,24 +649,20 @@ extern "C" int cra5_gemm_nt_split(const uint16_t *A, int lda_kp, const uint16_t 
   const bool a_plain = flags & CRA5_GEMM_A_PLAIN, w_plain = flags & CRA5_GEMM_W_PLAIN, o_plain = flags & CRA5_GEMM_OUT_PLAIN;
   const long lda = a_plain ? (long)lda_kp : 2L * lda_kp, ldw = w_plain ? (long)ldw_kp : 2L * ldw_kp;
   const long ldcs = o_plain ? (long)ldc_split_kp : 2L * ldc_split_kp;
-  // Long reductions (patch-embed conv, K = 29 480): K is cut into chunks of <= 8192 whose
-  // partial products are chained through the fp32 C matrix (C += A_i . W_i): a two-level
-  // sum (each chunk accumulates in the MFMA accumulators, chunks add in fp32) without a
-  // second accumulator register set, so the big tiles stay spill-free.
-  if (Kp > 8192 && C && !C_split && !(flags & CRA5_EPI_GELU)) {
-    const int nchunk = (Kp + 8191) / 8192;
-    const int gran = ((flags & CRA5_GEMM_HI_ONLY) && Kp % 64 == 0) ? 64 : 32;   // the wide reduced-precision form steps by 64
-    const int per = ((Kp / gran + nchunk - 1) / nchunk) * gran;
-    for (int k0 = 0, i = 0; k0 < Kp; k0 += per, ++i) {
-      const int kc = (Kp - k0 < per) ? Kp - k0 : per;
-      const int f = ((i == 0) ? flags : CRA5_EPI_RES) | (flags & (CRA5_GEMM_HI_ONLY | CRA5_GEMM_A_PLAIN | CRA5_GEMM_W_PLAIN));
-      const int rc = gemm_dispatch(A + (a_plain ? 1L : 2L) * k0, lda, W + (w_plain ? 1L : 2L) * k0, ldw, C, ldc, nullptr, 0, (i == 0) ? bias : nullptr,
-                                   (i == 0) ? res : C, (i == 0) ? ldr : ldc, M, N, kc, wscale_inv, f, st);
-      if (rc) return rc;
-    }
-    return 0;
+  if (!(form & CRA5_FORM_CHAINED))
+    return gemm_dispatch(form, A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
+  const int nchunk = (Kp + 8191) / 8192;
+  // (chunks are multiples of 64 whenever the reduced-precision mode's Kp is one: the wide form then holds in every chunk)
+  const int gran = ((flags & CRA5_GEMM_HI_ONLY) && Kp % 64 == 0) ? 64 : 32;
+  const int per = ((Kp / gran + nchunk - 1) / nchunk) * gran;
+  for (int k0 = 0, i = 0; k0 < Kp; k0 += per, ++i) {
+    const int kc = (Kp - k0 < per) ? Kp - k0 : per;
+    const int f = ((i == 0) ? flags : CRA5_EPI_RES) | (flags & (CRA5_GEMM_HI_ONLY | CRA5_GEMM_A_PLAIN | CRA5_GEMM_W_PLAIN));
+    const int rc = gemm_dispatch(form, A + (a_plain ? 1L : 2L) * k0, lda, W + (w_plain ? 1L : 2L) * k0, ldw, C, ldc, nullptr, 0,
+                                 (i == 0) ? bias : nullptr, (i == 0) ? res : C, (i == 0) ? ldr : ldc, M, N, kc, wscale_inv, f, st);
+    if (rc) return rc;
   }
-  return gemm_dispatch(A, lda, W, ldw, C, ldc, C_split, ldcs, bias, res, ldr, M, N, Kp, wscale_inv, flags, st);
+  return 0;
 }
 
 // Fixed-tile entry for the hyper-prior path (csrc/hyper.hip): 64 x 64 or 128 x 128 tiles chosen by the CALLER,
@@ -689,7 +694,7 @@ extern "C" size_t cra5_unembed_side_bytes(int C, int H, int W, int kh, int kw, i
 extern "C" int cra5_gemm_nt_split_unembed(const uint16_t *A, int lda_kp, const uint16_t *Wt, int ldw_kp, float *x,
                                           float *side, size_t side_bytes, const float *mean, const float *stdv, int M,
                                           int Kp, float wscale_inv, int C, int H, int W, int kh, int kw, int sh, int sw,
-                                          int hi_only, void *stream) {
+                                          int mode, void *stream) {
   const size_t need = cra5_unembed_side_bytes(C, H, W, kh, kw, sh, sw);
   if (!need) return CRA5_ERR_ARG;                       // other geometries: plain GEMM + cra5_col2im_f32
   if (!A || !Wt || !x || !side || side_bytes < need || M <= 0 || Kp <= 0 || (Kp % BK) || Kp > 8192) return CRA5_ERR_ARG;
@@ -707,21 +712,18 @@ extern "C" int cra5_gemm_nt_split_unembed(const uint16_t *A, int lda_kp, const u
   ue.W = W;
   ue.Hp = Hp;
   ue.Wp = Wp;
-  // hi_only: 0 = fp32-accurate; 1 = reduced precision on split operands; | 2: A is a plain f16 matrix, | 4: Wt is
-  // (pitches then in halves, as for cra5_gemm_nt_split's CRA5_GEMM_A_PLAIN / _W_PLAIN)
-  const bool a_plain = hi_only & 2, w_plain = hi_only & 4;
-  if ((a_plain || w_plain) && (!(hi_only & 1) || (Kp % 64))) return CRA5_ERR_ARG;
-  const long lda = a_plain ? (long)lda_kp : 2L * lda_kp, ldw = w_plain ? (long)ldw_kp : 2L * ldw_kp;
-  int rc;
-  if (hi_only && Kp % 64 == 0)
-    rc = launch<2, 4, 4, 2, false, 2, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv,
-                                               CRA5_GEMM_HI_ONLY | (a_plain ? CRA5_GEMM_A_PLAIN : 0) | (w_plain ? CRA5_GEMM_W_PLAIN : 0), st, ue);
-  else if (hi_only)
-    rc = launch<2, 4, 4, 2, false, 1, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv,
-                                               CRA5_GEMM_HI_ONLY, st, ue);
-  else
-    rc = launch<2, 4, 4, 2, false, 3, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv,
-                                               0, st, ue);
+  // mode: the CRA5_GEMM_* word - 0 = fp32-accurate; HI_ONLY = reduced precision, | A_PLAIN: A is a plain f16 matrix,
+  // | W_PLAIN: Wt is (pitches then in halves, as for cra5_gemm_nt_split).  The 256 x 256 tile in the form the rule
+  // gives a reduced-precision launch that asks for the wide form: 64-wide k-steps where it accepts, else 32-wide
+  constexpr int PLAIN_IN = CRA5_GEMM_A_PLAIN | CRA5_GEMM_W_PLAIN;
+  if ((mode & ~(CRA5_GEMM_HI_ONLY | PLAIN_IN)) || ((mode & PLAIN_IN) && !(mode & CRA5_GEMM_HI_ONLY))) return CRA5_ERR_ARG;
+  const int form = (mode & CRA5_GEMM_HI_ONLY) ? cra5_gemm_split_form(M, N, Kp, mode | CRA5_GEMM_WIDE_K, 1, 0) : 0;
+  if (form < 0 && (mode & PLAIN_IN)) return CRA5_ERR_ARG;
+  const long lda = (mode & CRA5_GEMM_A_PLAIN) ? (long)lda_kp : 2L * lda_kp, ldw = (mode & CRA5_GEMM_W_PLAIN) ? (long)ldw_kp : 2L * ldw_kp;
+#define CRA5_UE_GO(NP) \
+  launch<2, 4, 4, 2, false, NP, true>(A, lda, Wt, ldw, x, 0, nullptr, 0, nullptr, nullptr, 0, M, N, Kp, wscale_inv, mode, st, ue)
+  const int rc = (mode & CRA5_GEMM_HI_ONLY) ? (form >= 0 ? CRA5_UE_GO(2) : CRA5_UE_GO(1)) : CRA5_UE_GO(3);
+#undef CRA5_UE_GO
   if (rc) return rc;
   const size_t total = (size_t)C * (Hp + 1) * (W / 4);
   size_t g = (total + 255) / 256;

@@ -3,6 +3,7 @@ function passes raw `data_ptr()`s + sizes + the current HIP stream to the native
 library.  Device entry points refuse non-GPU tensors (no CPU fallback)."""
 import contextlib
 import ctypes
+import functools
 import os
 import threading
 
@@ -11,7 +12,10 @@ import torch
 
 from ._lib import check, lib
 
-EPI_BIAS, EPI_GELU, EPI_RES, GEMM_HI_ONLY = 1, 2, 4, 8
+EPI_BIAS, EPI_GELU, EPI_RES = 1, 2, 4                                                            # CRA5_EPI_*
+GEMM_HI_ONLY, GEMM_A_PLAIN, GEMM_W_PLAIN, GEMM_OUT_PLAIN, GEMM_WIDE_K = 8, 16, 32, 64, 128       # CRA5_GEMM_*: the mode word
+FORM_TILE, FORM_K64, FORM_CHAINED, FORM_PLAIN = 0x1c0, 1, 2, 4                                   # CRA5_FORM_*
+ERR_ARG = -7                                                                                     # CRA5_ERR_ARG
 
 
 _TLS = threading.local()
@@ -157,6 +161,21 @@ class KernelTimer:
 
 
 TIMER = None  # set to a KernelTimer by bench.py
+_UNTIMED = contextlib.nullcontext()
+
+
+@contextlib.contextmanager
+def _bracket(kind, work):
+    ev = TIMER.start()
+    yield
+    TIMER.stop(kind() if callable(kind) else kind, ev, work)
+
+
+def _timed(kind, work):
+    """`with _timed(kind, work):` around a launch: TIMER's event bracket, booked as `kind` (a name, or a function giving
+    it - called only when a timer runs) with `work` flops / bytes.  No timer: one shared no-op context."""
+    return _UNTIMED if TIMER is None else _bracket(kind, work)
+
 
 COPY_CHUNK = 32 << 20
 COPY_THREADS = 8     # host threads of one staged copy; cra5_api / VAEformer pass RuntimeConfig.copy_threads explicitly
@@ -219,12 +238,10 @@ def gemm_nt(a, w, bias=None, res=None, gelu=False, out=None):
     if out is None:
         out = torch.empty((M, N), device=a.device, dtype=torch.float32)
     flags = (EPI_BIAS if bias is not None else 0) | (EPI_GELU if gelu else 0) | (EPI_RES if res is not None else 0)
-    ev = TIMER.start() if TIMER is not None else None
-    check(lib().cra5_gemm_nt_f32(_p(a), _row_stride(a), _p(w), _row_stride(w), _p(out), _row_stride(out), _p(bias),
-                                 _p(res), _row_stride(res) if res is not None else 0, M, N, K, flags, _stream()),
-          "cra5_gemm_nt_f32")
-    if ev is not None:
-        TIMER.stop("gemm_nt_f32", ev, 2.0 * M * N * K)
+    with _timed("gemm_nt_f32", 2.0 * M * N * K):
+        check(lib().cra5_gemm_nt_f32(_p(a), _row_stride(a), _p(w), _row_stride(w), _p(out), _row_stride(out), _p(bias),
+                                     _p(res), _row_stride(res) if res is not None else 0, M, N, K, flags, _stream()),
+              "cra5_gemm_nt_f32")
     return out
 
 
@@ -278,12 +295,6 @@ class SplitMat:
         return ((h[:, :, 0] + h[:, :, 1]).reshape(self.rows, self.Kp)[:, : self.K]) * self.scale_inv
 
 
-def _devs(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("cra5_amd device op called with a non-GPU tensor: the HIP path is the only path")
-
-
 def split_f16(x, scale_pow2=None, out=None):
     """fp32 [rows, K] (row-strided ok) -> SplitMat.  scale_pow2: None = 1.0; 'auto' = the
     power of two that brings max|x| into [2^12, 2^13) (weights)."""
@@ -306,13 +317,38 @@ def split_f16(x, scale_pow2=None, out=None):
     return out
 
 
-GEMM_A_PLAIN, GEMM_W_PLAIN, GEMM_OUT_PLAIN, GEMM_WIDE_K = 16, 32, 64, 128
+@functools.lru_cache(maxsize=None)
+def gemm_form(M, N, Kp, flags=0, f32_out=True, split_out=False):
+    """cra5_gemm_split_form, memoised: the form cra5_gemm_nt_split gives a launch of this shape, these flags (EPI_* |
+    GEMM_*) and these outputs - its tile's rows (& FORM_TILE) | FORM_K64 | FORM_CHAINED | FORM_PLAIN - or ERR_ARG where
+    the launcher refuses.  THE rule lives in the library; nothing here or in the model restates it."""
+    return lib().cra5_gemm_split_form(M, N, Kp, flags, f32_out, split_out)
 
 
+@functools.lru_cache(maxsize=None)
 def plain_ok(M, N, Kp):
-    """Shapes on which cra5_gemm_nt_split takes plain-f16 operands / writes a plain output (the wide reduced-precision
-    form: big tiles, 64-wide k-steps, no long-K chain through a split output)."""
-    return ((M + 127) // 128) * ((N + 127) // 128) >= 256 and Kp % 64 == 0
+    """Shapes on which cra5_gemm_nt_split takes plain-f16 operands / writes a plain output in the reduced-precision mode
+    (the 64-wide k-step form by the launch's own size; Kp > 8192: the chained call, fp32 output alone)."""
+    return gemm_form(M, N, Kp, GEMM_HI_ONLY | GEMM_A_PLAIN | GEMM_W_PLAIN | GEMM_OUT_PLAIN) >= 0
+
+
+def _mode(hi_only, a=None, w=None, out_plain=False, wide_k=False):
+    """The CRA5_GEMM_* mode word of a launch reading the SplitMats a / w: the reduced-precision mode, which operands are
+    plain rows (their producers' tags), a plain split output, the forced 64-wide k-step form."""
+    m = ((GEMM_A_PLAIN if a is not None and a.plain else 0) | (GEMM_W_PLAIN if w is not None and w.plain else 0)
+         | (GEMM_OUT_PLAIN if out_plain else 0))
+    assert hi_only or not m, "plain-f16 operands exist in the reduced-precision mode only"
+    assert hi_only or not wide_k, "the 64-wide k-step form exists in the reduced-precision mode only"
+    return m | (GEMM_HI_ONLY if hi_only else 0) | (GEMM_WIDE_K if wide_k else 0)
+
+
+def _out_split(s, plain=False, gemm=False):
+    """(pointer, pitch) of the optional split-f16 destination `s` (a SplitMat or None) for the C ABI, tagging its rows
+    plain / split for its consumer.  The pitch is Kp; gemm: cra5_gemm_nt_split's, which counts a plain row in halves."""
+    if s is None:
+        return None, 0
+    s.plain = bool(plain)
+    return s.data.data_ptr(), s.pitch if gemm else s.Kp
 
 
 def gemm_nt_split(a, w, bias=None, res=None, gelu=False, out=None, out_split=None, want_f32=True, hi_only=False,
@@ -321,8 +357,7 @@ def gemm_nt_split(a, w, bias=None, res=None, gelu=False, out=None, out_split=Non
     want_f32=False; out_split: SplitMat [M, N] to receive the split-f16 result.  Reduced-precision mode (hi_only): a / w
     may be PLAIN matrices (SplitMat.plain) and out_plain=True writes out_split's rows plain; wide_k=True takes the
     64-wide k-step form (CRA5_GEMM_WIDE_K) at any size - the summation order of the big launches this one is a slice of."""
-    _devs(a.data, w.data)
-    _dev(bias, res, out)
+    _dev(a.data, w.data, bias, res, out)
     M, N = a.rows, w.rows
     assert a.Kp == w.Kp and a.K == w.K, (a.K, w.K)
     assert a.scale_inv == 1.0, "activations are split unscaled"
@@ -330,29 +365,19 @@ def gemm_nt_split(a, w, bias=None, res=None, gelu=False, out=None, out_split=Non
         out = torch.empty((M, N), device=a.data.device, dtype=torch.float32)
     if out_split is not None:
         assert out_split.rows == M and out_split.K == N
-    flags = (EPI_BIAS if bias is not None else 0) | (EPI_GELU if gelu else 0) | (EPI_RES if res is not None else 0)
-    if hi_only:
-        flags |= GEMM_HI_ONLY
-    if a.plain or w.plain or out_plain:
-        assert hi_only, "plain-f16 operands exist in the reduced-precision mode only"
-        flags |= (GEMM_A_PLAIN if a.plain else 0) | (GEMM_W_PLAIN if w.plain else 0) | (GEMM_OUT_PLAIN if out_plain else 0)
-    if wide_k:
-        assert hi_only, "the 64-wide k-step form exists in the reduced-precision mode only"
-        flags |= GEMM_WIDE_K
-    if out_split is not None:
-        out_split.plain = bool(out_plain)
-    ev = TIMER.start() if TIMER is not None else None
-    check(lib().cra5_gemm_nt_split(_p(a.data), a.pitch, _p(w.data), w.pitch, _p(out),
-                                   _row_stride(out) if out is not None else 0,
-                                   _p(out_split.data) if out_split is not None else None,
-                                   out_split.pitch if out_split is not None else 0, _p(bias), _p(res),
-                                   _row_stride(res) if res is not None else 0, M, N, a.Kp, float(w.scale_inv),
-                                   flags, _stream()), "cra5_gemm_nt_split")
-    if ev is not None:
-        # same rule as gemm_dispatch(): < 256 128x128 tiles -> the 64x64-tile instantiation (hyper-prior
-        # and head GEMMs: microseconds, launch-bound); everything else is the 192/256-row-tile kernel
-        small = ((M + 127) // 128) * ((N + 127) // 128) < 256
-        TIMER.stop("gemm_nt_split_small" if small else "gemm_nt_split", ev, 2.0 * M * N * a.K)
+    flags = ((EPI_BIAS if bias is not None else 0) | (EPI_GELU if gelu else 0) | (EPI_RES if res is not None else 0)
+             | _mode(hi_only, a, w, out_plain, wide_k))
+    cs, ldcs = _out_split(out_split, out_plain, gemm=True)
+
+    def kind():   # booked by the kernel that runs: the 64 x 64-tile instantiation (hyper-prior and head GEMMs:
+        # microseconds, launch-bound) apart from the big-tile kernels
+        small = gemm_form(M, N, a.Kp, flags, out is not None, out_split is not None) & FORM_TILE == 64
+        return "gemm_nt_split_small" if small else "gemm_nt_split"
+    with _timed(kind, 2.0 * M * N * a.K):
+        check(lib().cra5_gemm_nt_split(_p(a.data), a.pitch, _p(w.data), w.pitch, _p(out),
+                                       _row_stride(out) if out is not None else 0, cs, ldcs, _p(bias), _p(res),
+                                       _row_stride(res) if res is not None else 0, M, N, a.Kp, float(w.scale_inv),
+                                       flags, _stream()), "cra5_gemm_nt_split")
     return out
 
 
@@ -364,21 +389,16 @@ def unembed_side_bytes(C, H, W, kh, kw, sh, sw):
 def gemm_unembed(a, w, C, H, W, kh, kw, sh, sw, side, mean=None, std=None, out=None, hi_only=False):
     """Fused un-embed (cra5_gemm_nt_split_unembed): a SplitMat [Hp*Wp, K] (tokens), w SplitMat [C*kh*kw, K] -> the image
     x [C, H, W] (de-normalised when mean / std are given).  `side`: device float buffer of >= unembed_side_bytes()."""
-    _devs(a.data, w.data)
-    _dev(side, mean, std, out)
+    _dev(a.data, w.data, side, mean, std, out)
     assert a.Kp == w.Kp and a.K == w.K and w.rows == C * kh * kw and a.scale_inv == 1.0
     if out is None:
         out = torch.empty((C, H, W), device=a.data.device, dtype=torch.float32)
     assert out.is_contiguous() and tuple(out.shape) == (C, H, W) and side.is_contiguous()
-    ev = TIMER.start() if TIMER is not None else None
-    hi = (1 if hi_only else 0) | (2 if a.plain else 0) | (4 if w.plain else 0)
-    assert hi in (0, 1) or hi_only, "plain-f16 operands exist in the reduced-precision mode only"
-    check(lib().cra5_gemm_nt_split_unembed(_p(a.data), a.pitch, _p(w.data), w.pitch, _p(out), _p(side),
-                                           side.numel() * side.element_size(), _p(mean), _p(std), a.rows, a.Kp,
-                                           float(w.scale_inv), C, H, W, kh, kw, sh, sw, hi, _stream()),
-          "cra5_gemm_nt_split_unembed")
-    if ev is not None:
-        TIMER.stop("gemm_nt_split", ev, 2.0 * a.rows * w.rows * a.K)
+    with _timed("gemm_nt_split", 2.0 * a.rows * w.rows * a.K):
+        check(lib().cra5_gemm_nt_split_unembed(_p(a.data), a.pitch, _p(w.data), w.pitch, _p(out), _p(side),
+                                               side.numel() * side.element_size(), _p(mean), _p(std), a.rows, a.Kp,
+                                               float(w.scale_inv), C, H, W, kh, kw, sh, sw, _mode(hi_only, a, w), _stream()),
+              "cra5_gemm_nt_split_unembed")
     return out
 
 
@@ -386,8 +406,7 @@ def small_gemm_nt_split(a, w, bias=None, res=None, gelu=False, out=None, out_spl
                         unembed=None):
     """gemm_nt_split for the hyper-prior sizes (csrc/hyper.hip).  unembed = (Hz, Wz, p1, p2): `out` is the
     image [N / (p1*p2), Hz*p1, Wz*p2] and w's rows are in (c, p1, p2) order (HyperpriorDecoder un-embed)."""
-    _devs(a.data, w.data)
-    _dev(bias, res, out)
+    _dev(a.data, w.data, bias, res, out)
     M, N = a.rows, w.rows
     assert a.Kp == w.Kp and a.K == w.K, (a.K, w.K)
     assert a.scale_inv == 1.0, "activations are split unscaled"
@@ -401,17 +420,12 @@ def small_gemm_nt_split(a, w, bias=None, res=None, gelu=False, out=None, out_spl
     if out_split is not None:
         assert out_split.rows == M and out_split.K == N
     flags = (EPI_BIAS if bias is not None else 0) | (EPI_GELU if gelu else 0) | (EPI_RES if res is not None else 0)
-    ev = TIMER.start() if TIMER is not None else None
-    if out_split is not None:
-        out_split.plain = False      # (split rows: workspace matrices change layout with the mode)
-    check(lib().cra5_small_gemm_nt_split(_p(a.data), a.Kp, _p(w.data), w.Kp, _p(out),
-                                         _row_stride(out) if (out is not None and unembed is None) else 0,
-                                         _p(out_split.data) if out_split is not None else None,
-                                         out_split.Kp if out_split is not None else 0, _p(bias), _p(res),
-                                         _row_stride(res) if res is not None else 0, M, N, a.Kp, float(w.scale_inv),
-                                         flags, Hz, Wz, p1, p2, _stream()), "cra5_small_gemm_nt_split")
-    if ev is not None:
-        TIMER.stop("gemm_nt_split_small", ev, 2.0 * M * N * a.K)
+    cs, ldcs = _out_split(out_split)      # (split rows: workspace matrices change layout with the mode)
+    with _timed("gemm_nt_split_small", 2.0 * M * N * a.K):
+        check(lib().cra5_small_gemm_nt_split(_p(a.data), a.Kp, _p(w.data), w.Kp, _p(out),
+                                             _row_stride(out) if (out is not None and unembed is None) else 0, cs, ldcs,
+                                             _p(bias), _p(res), _row_stride(res) if res is not None else 0, M, N, a.Kp,
+                                             float(w.scale_inv), flags, Hz, Wz, p1, p2, _stream()), "cra5_small_gemm_nt_split")
     return out
 
 
@@ -425,14 +439,10 @@ def hyper_attention(qkv, heads, out=None, out_split=None, want_f32=True):
         out = torch.empty((n, C), device=qkv.device, dtype=torch.float32)
     if out_split is not None:
         assert out_split.rows == n and out_split.K == C
-    ev = TIMER.start() if TIMER is not None else None
-    if out_split is not None:
-        out_split.plain = False      # (split rows: workspace matrices change layout with the mode)
-    check(lib().cra5_hyper_attention_f32(_p(qkv), _p(out), _p(out_split.data) if out_split is not None else None,
-                                         out_split.Kp if out_split is not None else 0, n, C, heads,
-                                         float((C // heads) ** -0.5), _stream()), "cra5_hyper_attention_f32")
-    if ev is not None:
-        TIMER.stop("hyper_attention_f32", ev, 4.0 * n * n * C)
+    os_, ldos = _out_split(out_split)
+    with _timed("hyper_attention_f32", 4.0 * n * n * C):
+        check(lib().cra5_hyper_attention_f32(_p(qkv), _p(out), os_, ldos, n, C, heads, float((C // heads) ** -0.5),
+                                             _stream()), "cra5_hyper_attention_f32")
     return out if out is not None else out_split
 
 
@@ -443,19 +453,14 @@ def layernorm(x, gamma, beta, eps=1e-6, out=None, out_split=None, want_f32=True,
         out = torch.empty((rows, D), device=x.device, dtype=torch.float32)
     if out_split is not None:
         assert out_split.rows == rows and out_split.K == D
-    ev = TIMER.start() if TIMER is not None else None
-    check(lib().cra5_layernorm_f32(_p(x), _row_stride(x), _p(gamma), _p(beta), _p(out),
-                                   _row_stride(out) if out is not None else 0,
-                                   _p(out_split.data) if out_split is not None else None,
-                                   out_split.Kp if out_split is not None else 0, rows, D, float(eps),
-                                   int(bool(out_plain)), _stream()),
-          "cra5_layernorm_f32")
-    if out_split is not None:
-        out_split.plain = bool(out_plain)
-    if ev is not None:   # bytes: the row read once + every output written once
-        # (the 648-row hyper-prior LayerNorms are launch-latency-bound: kept out of the HBM-bound figure)
-        TIMER.stop("layernorm" if rows >= 4096 else "layernorm_small", ev,
-                   4.0 * rows * D * (1 + (out is not None) + (out_split is not None)))
+    ys, ldys = _out_split(out_split, out_plain)
+    # bytes: the row read once + every output written once
+    # (the 648-row hyper-prior LayerNorms are launch-latency-bound: kept out of the HBM-bound figure)
+    with _timed("layernorm" if rows >= 4096 else "layernorm_small",
+                4.0 * rows * D * (1 + (out is not None) + (out_split is not None))):
+        check(lib().cra5_layernorm_f32(_p(x), _row_stride(x), _p(gamma), _p(beta), _p(out),
+                                       _row_stride(out) if out is not None else 0, ys, ldys, rows, D, float(eps),
+                                       int(bool(out_plain)), _stream()), "cra5_layernorm_f32")
     return out if out is not None else out_split
 
 
@@ -472,17 +477,11 @@ def window_attention(qkv, pad_row, heads, H, W, wh, ww, out=None, out_split=None
     if out_split is not None:
         assert out_split.rows == N and out_split.K == C
     scale = float((C // heads) ** -0.5)
-    ev = TIMER.start() if TIMER is not None else None
-    if out_split is not None:
-        out_split.plain = False      # (split rows: workspace matrices change layout with the mode)
-    check(lib().cra5_window_attention_f32(_p(qkv), _p(pad_row), _p(out),
-                                          _p(out_split.data) if out_split is not None else None,
-                                          out_split.Kp if out_split is not None else 0, C, heads, H, W, wh, ww,
-                                          scale, _stream()), "cra5_window_attention_f32")
-    if ev is not None:
-        # algorithmic flops: real (unpadded) queries x all keys of their window, QK^T + PV
-        L = wh * ww
-        TIMER.stop("window_attention_f32", ev, 4.0 * N * L * C)
+    os_, ldos = _out_split(out_split)
+    # algorithmic flops: real (unpadded) queries x all keys of their window, QK^T + PV
+    with _timed("window_attention_f32", 4.0 * N * (wh * ww) * C):
+        check(lib().cra5_window_attention_f32(_p(qkv), _p(pad_row), _p(out), os_, ldos, C, heads, H, W, wh, ww, scale,
+                                              _stream()), "cra5_window_attention_f32")
     return out if out is not None else out_split
 
 
@@ -503,41 +502,26 @@ def window_attention_split(qkv_s, pad_s, heads, H, W, wh, ww, out=None, out_spli
     """qkv_s: SplitMat [H*W, 3C]; pad_s: SplitMat [1, 3C] (the split qkv bias).  workspace: a device byte tensor
     of >= attention_workspace_bytes(H*W, heads) -> the balanced schedule for whole-grid launches (balanced=True with
     workspace=None: a plan that needs no workspace)."""
-    _devs(qkv_s.data, pad_s.data)
-    _dev(out)
+    _dev(qkv_s.data, pad_s.data, out)
     N, C = qkv_s.rows, qkv_s.K // 3
     assert N == H * W and qkv_s.Kp == 3 * C and pad_s.Kp == 3 * C
     if out_split is not None:
         assert out_split.rows == N and out_split.K == C
     scale = float((C // heads) ** -0.5)
-    # reduced-precision mode on PLAIN rows (hi_only = 3 in the C ABI): the qkv GEMM wrote them plain; the pad row must be
-    # plain too and out_split is written plain
-    hi_flag = int(bool(hi_only))
-    if qkv_s.plain:
-        assert hi_only and pad_s.plain, "plain qkv rows need the reduced-precision mode and a plain pad row"
-        hi_flag = 3
-    else:
-        assert not pad_s.plain
-    if out_split is not None:
-        out_split.plain = hi_flag == 3
-    ev = TIMER.start() if TIMER is not None else None
-    if workspace is not None or balanced:
-        assert workspace is None or (workspace.is_cuda and workspace.is_contiguous())
-        check(lib().cra5_window_attention_split_ws(_p(qkv_s.data), qkv_s.Kp, _p(pad_s.data), _p(out),
-                                                   _p(out_split.data) if out_split is not None else None,
-                                                   out_split.Kp if out_split is not None else 0, C, heads, H, W, wh, ww,
-                                                   scale, hi_flag,
-                                                   ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None,
-                                                   workspace.numel() * workspace.element_size() if workspace is not None else 0,
-                                                   _stream()),
-              "cra5_window_attention_split_ws")
-    else:
-        check(lib().cra5_window_attention_split(_p(qkv_s.data), qkv_s.Kp, _p(pad_s.data), _p(out),
-                                                _p(out_split.data) if out_split is not None else None,
-                                                out_split.Kp if out_split is not None else 0, C, heads, H, W, wh, ww,
-                                                scale, hi_flag, _stream()), "cra5_window_attention_split")
-    if ev is not None:
-        TIMER.stop("window_attention_split", ev, 4.0 * N * (wh * ww) * C)
+    # reduced-precision mode on PLAIN rows: the qkv GEMM wrote them plain; the pad row must be plain too and out_split is
+    # written plain
+    assert pad_s.plain == qkv_s.plain and (hi_only or not qkv_s.plain), \
+        "plain qkv rows need the reduced-precision mode and a plain pad row"
+    args = (_p(qkv_s.data), qkv_s.Kp, _p(pad_s.data), _p(out), *_out_split(out_split, qkv_s.plain), C, heads, H, W, wh, ww,
+            scale, _mode(hi_only, qkv_s, out_plain=qkv_s.plain))
+    with _timed("window_attention_split", 4.0 * N * (wh * ww) * C):
+        if workspace is not None or balanced:
+            assert workspace is None or (workspace.is_cuda and workspace.is_contiguous())
+            check(lib().cra5_window_attention_split_ws(*args, _p(workspace),
+                                                       workspace.numel() * workspace.element_size() if workspace is not None else 0,
+                                                       _stream()), "cra5_window_attention_split_ws")
+        else:
+            check(lib().cra5_window_attention_split(*args, _stream()), "cra5_window_attention_split")
     return out if out is not None else out_split
 
 
@@ -563,12 +547,10 @@ def im2col(x, kh, kw, sh, sw, ldk=None, mean=None, std=None, out=None, out_split
     assert x.is_contiguous()
     if out_split is not None:
         assert out_split.rows == Hp * Wp and out_split.K == K
-        ev = TIMER.start() if TIMER is not None else None
-        out_split.plain = bool(out_plain)
-        check(lib().cra5_im2col_f32(_p(x), _p(mean), _p(std), None, _p(out_split.data), C, H, W, kh, kw, sh, sw, Hp,
-                                    Wp, out_split.Kp, int(bool(out_plain)), _stream()), "cra5_im2col_f32")
-        if ev is not None:   # bytes: the frame read once + the patch matrix written once
-            TIMER.stop("im2col", ev, 4.0 * C * H * W + 4.0 * Hp * Wp * K)
+        cs, ldk = _out_split(out_split, out_plain)
+        with _timed("im2col", 4.0 * C * H * W + 4.0 * Hp * Wp * K):   # bytes: the frame read once + the patch matrix written once
+            check(lib().cra5_im2col_f32(_p(x), _p(mean), _p(std), None, cs, C, H, W, kh, kw, sh, sw, Hp, Wp, ldk,
+                                        int(bool(out_plain)), _stream()), "cra5_im2col_f32")
         return out_split
     ldk = ldk or K
     if out is None:
@@ -585,11 +567,9 @@ def col2im(cols, C, kh, kw, sh, sw, Hp, Wp, mean=None, std=None, out=None):
     if out is None:
         out = torch.empty((C, H, W), device=cols.device, dtype=torch.float32)
     assert out.is_contiguous()
-    ev = TIMER.start() if TIMER is not None else None
-    check(lib().cra5_col2im_f32(_p(cols), _p(mean), _p(std), _p(out), C, H, W, kh, kw, sh, sw, Hp, Wp,
-                                _row_stride(cols), _stream()), "cra5_col2im_f32")
-    if ev is not None:   # bytes: the column matrix read once + the frame written once
-        TIMER.stop("col2im", ev, 4.0 * Hp * Wp * C * kh * kw + 4.0 * C * H * W)
+    with _timed("col2im", 4.0 * Hp * Wp * C * kh * kw + 4.0 * C * H * W):   # bytes: the column matrix read once + the frame written once
+        check(lib().cra5_col2im_f32(_p(cols), _p(mean), _p(std), _p(out), C, H, W, kh, kw, sh, sw, Hp, Wp,
+                                    _row_stride(cols), _stream()), "cra5_col2im_f32")
     return out
 
 
@@ -602,7 +582,7 @@ def gather_token_rows(src, out, Hp, Wp, ti0, n_ti, tj0, n_tj, ti_step=None, tj_s
     if isinstance(src, SplitMat):
         if not isinstance(out, SplitMat) or out.Kp != src.Kp or out.K != src.K or out.rows != n_ti * n_tj:
             raise ValueError("gather_token_rows: `out` must be a SplitMat of n_ti * n_tj rows and src's K")
-        _devs(src.data, out.data)
+        _dev(src.data, out.data)
         row_bytes = 2 * src.Kp if src.plain else 4 * src.Kp       # a plain row holds Kp halves, a split row 2 * Kp
         s_t, d_t = src.data, out.data
         out.scale_inv, out.plain = src.scale_inv, src.plain
@@ -645,11 +625,9 @@ def strided_scatter(g, rows, cols, cls, n_cc, C, mean=None, std=None, out=None):
         out = torch.empty((C, Ho, Wo), device=g.device, dtype=torch.float32)
     if not (out.is_contiguous() and tuple(out.shape) == (C, Ho, Wo)):
         raise ValueError(f"strided_scatter: out must be a contiguous [{C}, {Ho}, {Wo}] tensor")
-    ev = TIMER.start() if TIMER is not None else None
-    check(lib().cra5_strided_scatter_f32(_p(g), g.numel(), _p(rows), _p(cols), _p(cls), cls.shape[0] // n_cc, n_cc,
-                                         _p(mean), _p(std), _p(out), C, Ho, Wo, _stream()), "cra5_strided_scatter_f32")
-    if ev is not None:
-        TIMER.stop("strided_scatter", ev, 8.0 * C * Ho * Wo)
+    with _timed("strided_scatter", 8.0 * C * Ho * Wo):
+        check(lib().cra5_strided_scatter_f32(_p(g), g.numel(), _p(rows), _p(cols), _p(cls), cls.shape[0] // n_cc, n_cc,
+                                             _p(mean), _p(std), _p(out), C, Ho, Wo, _stream()), "cra5_strided_scatter_f32")
     return out
 
 
@@ -662,10 +640,8 @@ def crop(src, r0, Hb, c0, Wb, out=None):
         out = torch.empty((C, Hb, Wb), device=src.device, dtype=torch.float32)
     if not (src.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (C, Hb, Wb)):
         raise ValueError(f"crop: src must be contiguous and out a contiguous [{C}, {Hb}, {Wb}] tensor")
-    ev = TIMER.start() if TIMER is not None else None
-    check(lib().cra5_crop_f32(_p(src), C, Hs, Ws, _p(out), r0, Hb, c0, Wb, _stream()), "cra5_crop_f32")
-    if ev is not None:
-        TIMER.stop("crop", ev, 8.0 * C * Hb * Wb)
+    with _timed("crop", 8.0 * C * Hb * Wb):
+        check(lib().cra5_crop_f32(_p(src), C, Hs, Ws, _p(out), r0, Hb, c0, Wb, _stream()), "cra5_crop_f32")
     return out
 
 
@@ -743,10 +719,8 @@ def _window_reduce(what, x, t, out, chan_map, launch):
     if not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (C_out, Ho, Wo)
             and out.device == x.device):
         raise ValueError(f"{what}: out must be a contiguous fp32 [{C_out}, {Ho}, {Wo}] tensor on x's device")
-    ev = TIMER.start() if TIMER is not None else None
-    launch(C, C_out, out, (sr0, sr1 - sr0, sc0, snc), (H, W))
-    if ev is not None:
-        TIMER.stop(what, ev, 4.0 * (C_out * (sr1 - sr0) * snc + C_out * Ho * Wo))
+    with _timed(what, 4.0 * (C_out * (sr1 - sr0) * snc + C_out * Ho * Wo)):
+        launch(C, C_out, out, (sr0, sr1 - sr0, sc0, snc), (H, W))
     return out
 
 
@@ -1004,10 +978,8 @@ def residual_quantize(x, x_hat, tol):
     counts = torch.empty((spans, 2), device=dev, dtype=torch.int32)
     offs = torch.empty((spans + 1, 2), device=dev, dtype=torch.int32)
     chan = torch.empty((C, 2), device=dev, dtype=torch.int64)
-    ev = TIMER.start() if TIMER else None
-    check(lib().cra5_residual_count_f32(_p(x), _p(x_hat), _p(tol_d), C, H, W, _p(counts), _stream()), "cra5_residual_count_f32")
-    if TIMER:
-        TIMER.stop("residual_count", ev, 8.0 * C * H * W)
+    with _timed("residual_count", 8.0 * C * H * W):
+        check(lib().cra5_residual_count_f32(_p(x), _p(x_hat), _p(tol_d), C, H, W, _p(counts), _stream()), "cra5_residual_count_f32")
     check(lib().cra5_residual_scan(_p(counts), C, H, W, _p(offs), _p(chan), _stream()), "cra5_residual_scan")
     per_channel = chan.cpu().numpy()
     n, m = (int(v) for v in per_channel.sum(axis=0))
@@ -1015,12 +987,10 @@ def residual_quantize(x, x_hat, tol):
     q = torch.empty((n,), device=dev, dtype=torch.int16)
     eidx = torch.empty((m,), device=dev, dtype=torch.int32)
     ebits = torch.empty((m,), device=dev, dtype=torch.int32)
-    ev = TIMER.start() if TIMER else None
-    check(lib().cra5_residual_emit_f32(_p(x), _p(x_hat), _p(tol_d), C, H, W, _p(offs), _p(idx) if n else None,
-                                       _p(q) if n else None, n, _p(eidx) if m else None, _p(ebits) if m else None, m,
-                                       _stream()), "cra5_residual_emit_f32")
-    if TIMER:
-        TIMER.stop("residual_emit", ev, 8.0 * C * H * W)
+    with _timed("residual_emit", 8.0 * C * H * W):
+        check(lib().cra5_residual_emit_f32(_p(x), _p(x_hat), _p(tol_d), C, H, W, _p(offs), _p(idx) if n else None,
+                                           _p(q) if n else None, n, _p(eidx) if m else None, _p(ebits) if m else None, m,
+                                           _stream()), "cra5_residual_emit_f32")
     return idx, q, eidx, ebits, per_channel
 
 
@@ -1079,12 +1049,10 @@ def residual_apply(out, records, step, grid, chan_lut=None, box=None, stride=Non
     idx, q, eidx, ebits = _residual_records(what, records, out.device)
     _residual_array(what, "step", step, torch.float32, out.device, (C,))
     n, m = idx.numel(), eidx.numel()
-    ev = TIMER.start() if TIMER else None
-    check(lib().cra5_residual_apply_f32(_p(out), *geom, _p(step), _p(idx) if n else None, _p(q) if n else None, n,
-                                        _p(eidx) if m else None, _p(ebits) if m else None, m, _stream()),
-          "cra5_residual_apply_f32")
-    if TIMER:
-        TIMER.stop("residual_apply", ev, 14.0 * n + 16.0 * m)
+    with _timed("residual_apply", 14.0 * n + 16.0 * m):
+        check(lib().cra5_residual_apply_f32(_p(out), *geom, _p(step), _p(idx) if n else None, _p(q) if n else None, n,
+                                            _p(eidx) if m else None, _p(ebits) if m else None, m, _stream()),
+              "cra5_residual_apply_f32")
     return out
 
 

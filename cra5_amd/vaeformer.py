@@ -808,9 +808,8 @@ class VAEformer(nn.Module):
                  bias=self.post_quant_conv.bias, out=t)
         for j, blk in enumerate(self.g_s.blocks):
             self._block(blk, f"g_s.blocks.{j}", t, t, (self.Hp, self.Wp))
-        Cout, (Himg, Wimg) = cfg['out_chans'], cfg['img_size']
-        # the LayerNorm writes plain rows when the whole frame's un-embed would take them (a subset's geometry may not)
-        h = self._ln(t, self.g_s.norm, f"h{D}", plain=self._fused_unembed_form(Cout, Himg, Wimg)[1])
+        # the LayerNorm writes plain rows when the whole frame's un-embed takes them (a subset follows the full launch)
+        h = self._ln(t, self.g_s.norm, f"h{D}", plain=self._unembed_launch()[3])
         return self._unembed(h, mean, std, channels, box, step, out, coarsen=coarsen, regrid=regrid)
 
     # ---- un-embed: the whole frame, or chosen channels and / or a lat-lon box of it ---------------------------
@@ -994,17 +993,37 @@ class VAEformer(nn.Module):
                              f"{tuple(out.shape)} {out.dtype} on {out.device}")
         return out
 
-    def _fused_unembed_form(self, C, H, W):
-        """The un-embed of a [C, H, W] image: -> (nside, plain).  nside > 0: ONE fused launch pair runs - the GEMM
-        epilogue scatters into the image (de-normalised), the overlap rows go through a side buffer of nside bytes (no
-        [tokens][C*kh*kw] column matrix, no overlap-add pass); 0: the two-call form (GEMM + col2im).  plain: the fused
-        launch (always the 256 x 256 wide form) takes plain-f16 A rows (reduced precision, plain layout, D % 64 == 0)."""
+    def _fused_unembed_side(self, C, H, W):
+        """The un-embed of a [C, H, W] image: nside > 0: ONE fused launch pair runs - the GEMM epilogue scatters into the
+        image (de-normalised), the overlap rows go through a side buffer of nside bytes (no [tokens][C*kh*kw] column
+        matrix, no overlap-add pass); 0: the two-call form (GEMM + col2im)."""
         cfg = self.cfg
-        D = cfg['embed_dim']
         (kh, kw), (sh, sw) = cfg['patch_size'], cfg['patch_stride']
-        nside = (ops.unembed_side_bytes(C, H, W, kh, kw, sh, sw)
-                 if self.gemm_mode == "split" and self.fused_unembed and D <= 8192 else 0)
-        return nside, bool(nside) and self._hi("g_s.final") and self.f16_layout == "plain" and D % 64 == 0
+        return (ops.unembed_side_bytes(C, H, W, kh, kw, sh, sw)
+                if self.gemm_mode == "split" and self.fused_unembed and cfg['embed_dim'] <= 8192 else 0)
+
+    def _unembed_launch(self):
+        """The FULL decode's un-embed launch -> (kind, hi, wide, a_plain): the weight copy it reads ("f32" / "split" /
+        "plain"), the reduced-precision mode, the 64-wide k-step form (ops.gemm_form: the fused pair asks for it,
+        CRA5_GEMM_WIDE_K, the two-call GEMM of Hp * Wp tokens x C * kh * kw columns takes it by its size), plain A rows
+        (the fused pair's alone).  A subset, thinned, coarsened or regridded decode names this launch, whatever its own
+        geometry: that is its promise of the full decode's bits."""
+        if self.gemm_mode != "split":
+            return "f32", False, False, False
+        cfg = self.cfg
+        Cout, (Himg, Wimg), (kh, kw) = cfg['out_chans'], cfg['img_size'], cfg['patch_size']
+        hi = self._hi("g_s.final")
+        fused = bool(self._fused_unembed_side(Cout, Himg, Wimg))
+        form = ops.gemm_form(self.Hp * self.Wp, Cout * kh * kw, _rup(cfg['embed_dim'], 32),
+                             ops.GEMM_HI_ONLY | (ops.GEMM_WIDE_K if fused else 0)) if hi else 0
+        wide = form > 0 and bool(form & ops.FORM_K64)
+        plain = wide and self.f16_layout == "plain"
+        return ("plain" if plain else "split"), hi, wide, fused and plain
+
+    def _unembed_weight(self, kind):
+        """The cached copy `kind` (_unembed_launch) of the WHOLE un-embed weight."""
+        key, w = "g_s.final", self.g_s.final.weight
+        return {"f32": self._wf32, "split": self._wsplit, "plain": self._wplain}[kind](key, w)
 
     def _unembed(self, h, mean, std, chans, box, step=None, out=None, coarsen=None, regrid=None):
         """The un-embed for channels `chans` (tuple | None: all) inside grid box `box` (tuple | None: the whole grid),
@@ -1044,30 +1063,23 @@ class VAEformer(nn.Module):
         Hs, Ws = p["Hs"], p["Ws"]
         out = self._frame_dest(out, (Cs, p["Hb"], p["Wb"]))
         sup = out if p["exact"] else self._buf("ue_sup", (Cs, Hs, Ws))
-        key, w = "g_s.final", self.g_s.final.weight
-        nside = self._fused_unembed_form(Cs, Hs, Ws)[0]
+        # the weight copy, mode and k-step form of the FULL decode's launch, whatever this geometry
+        kind, hi, wide, _ = self._unembed_launch()
+        wfull = self._unembed_weight(kind)
+        wg = wfull if chans is None else self._rows_of_channels(kind, wfull, chans)
+        nside = self._fused_unembed_side(Cs, Hs, Ws)
         if nside:
             # a subset runs the full decode's launch pair on the superset geometry (H = 10 n_ti + 1, W = 10 n_tj)
             side = self._buf("ue_side" + sub, (nside // 4,))
-            wfull = self._wplain(key, w) if h.plain else self._wsplit(key, w)
-            wue = wfull if chans is None else self._rows_of_channels("plain" if h.plain else "split", wfull, chans)
-            ops.gemm_unembed(a, wue, Cs, Hs, Ws, kh, kw, sh, sw, side, mean=ms, std=ss, out=sup, hi_only=self._hi(key))
+            ops.gemm_unembed(a, wg, Cs, Hs, Ws, kh, kw, sh, sw, side, mean=ms, std=ss, out=sup, hi_only=hi)
         else:
             cols = self._buf("ue_cols" + sub, (M, Cs * kh * kw))
             if split:
-                # the full decode's GEMM is ONE launch of M = Hp * Wp tokens x N = C * kh * kw columns: a subset reads
-                # the weight copy of that shape and takes its summation order (CRA5_GEMM_WIDE_K), whatever its own size.
-                # The full launch itself sets no flag: it takes that form by its size (and the flag refuses Kp > 8192).
-                Mf, Nf = Hp * Wp, Cout * kh * kw
-                wsp = self._wsplit(key, w)
-                hi = self._hi(key)
-                kind = "plain" if self._plain_gemm(key, Mf, Nf, wsp.K) else "split"
-                wfull = self._wplain(key, w) if kind == "plain" else wsp
-                wg = wfull if chans is None else self._rows_of_channels(kind, wfull, chans)
-                ops.gemm_nt_split(a, wg, out=cols, hi_only=hi, wide_k=hi and sub != "" and ops.plain_ok(Mf, Nf, wsp.Kp))
+                # the full decode's GEMM is ONE launch of M = Hp * Wp tokens x N = C * kh * kw columns: a subset names its
+                # summation order (CRA5_GEMM_WIDE_K).  The full launch itself sets no flag: it takes that form by its
+                # size (and the flag refuses Kp > 8192).
+                ops.gemm_nt_split(a, wg, out=cols, hi_only=hi, wide_k=wide and sub != "")
             else:
-                wf = self._wf32(key, w)
-                wg = wf if chans is None else self._rows_of_channels("f32", wf, chans)
                 ops.gemm_nt(a, wg, out=cols)
             ops.col2im(cols, Cs, kh, kw, sh, sw, p["n_ti"], p["n_tj"], mean=ms, std=ss, out=sup)
         if not p["exact"]:
@@ -1101,20 +1113,9 @@ class VAEformer(nn.Module):
         p, tb, tdev = self._sub_cached(("plan", self.device, box, step, Cs), self, make_plan)
         rcs, ccs = p["row_classes"], p["col_classes"]
         ms, ss = self._stats_of_channels(mean, chans), self._stats_of_channels(std, chans)
-        key, w = "g_s.final", self.g_s.final.weight
-        Mf, Nf = Hp * Wp, Cout * kh * kw
-        hi = wide = False
-        if split:
-            # the weight copy and k-step form of the full decode's launch (fused pair or two-call form, _unembed)
-            wsp = self._wsplit(key, w)
-            hi = self._hi(key)
-            if self._fused_unembed_form(Cout, Himg, Wimg)[0]:
-                kind, wide = ("plain" if h.plain else "split"), hi and wsp.Kp % 64 == 0
-            else:
-                kind, wide = ("plain" if self._plain_gemm(key, Mf, Nf, wsp.K) else "split"), hi and ops.plain_ok(Mf, Nf, wsp.Kp)
-            wfull = self._wplain(key, w) if kind == "plain" else wsp
-        else:
-            kind, wfull = "f32", self._wf32(key, w)
+        # the weight copy and k-step form of the full decode's launch (fused pair or two-call form, _unembed)
+        kind, hi, wide, _ = self._unembed_launch()
+        wfull = self._unembed_weight(kind)
         taps = (tuple(rc["taps"] for rc in rcs), tuple(cc["taps"] for cc in ccs))
         cch = chans if chans is not None else range(Cout)
 

@@ -134,20 +134,24 @@ int cra5_pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *
 #define CRA5_EPI_BIAS 1
 #define CRA5_EPI_GELU 2
 #define CRA5_EPI_RES 4
-/* cra5_gemm_nt_split only: reduced-precision mode, hi.hi product only (plain f16 operands, fp32
- * accumulate, 1 MFMA per product instead of 3) - BASELINE.json configs[4], RMSE-gated.  Only the hi plane of
- * A / W is read, and only the hi plane of C_split is WRITTEN (its lo halves keep whatever they held: a
- * consumer of that matrix must run in this mode too). */
+/* The mode word of the split-f16 engine: cra5_gemm_nt_split takes these bits in `flags` beside the CRA5_EPI_* ones,
+ * cra5_gemm_nt_split_unembed and cra5_window_attention_split[_ws] take them as their `mode` (each names the words it
+ * accepts; any other word is CRA5_ERR_ARG before a launch).
+ * CRA5_GEMM_HI_ONLY: reduced-precision mode, hi.hi product only (plain f16 operands, fp32 accumulate, 1 MFMA per
+ * product instead of 3) - BASELINE.json configs[4], RMSE-gated.  Only the hi plane of A / W is read, and only the hi
+ * plane of C_split is WRITTEN (its lo halves keep whatever they held: a consumer of that matrix must run in this mode
+ * too). */
 #define CRA5_GEMM_HI_ONLY 8
-/* With CRA5_GEMM_HI_ONLY (big tiles, Kp % 64 == 0; CRA5_ERR_ARG otherwise): the operand / the split output is a PLAIN f16
- * matrix - a row is its k-values as contiguous halves (`lda_kp` / `ldw_kp` / `ldc_split_kp` then count HALVES per row:
- * a plain row may live in the first half of a split-layout row, pitch 2 * Kp).  One full 128-byte line per row and
- * 64-wide k-step instead of two half-lines: -13..-18 % per launch, bit-identical results. */
+/* With CRA5_GEMM_HI_ONLY, where the launch takes 64-wide k-steps (cra5_gemm_split_form; CRA5_ERR_ARG otherwise): the
+ * operand / the split output is a PLAIN f16 matrix - a row is its k-values as contiguous halves (`lda_kp` / `ldw_kp` /
+ * `ldc_split_kp` then count HALVES per row: a plain row may live in the first half of a split-layout row, pitch
+ * 2 * Kp).  One full 128-byte line per row and 64-wide k-step instead of two half-lines: -13..-18 % per launch,
+ * bit-identical results. */
 #define CRA5_GEMM_A_PLAIN 16
 #define CRA5_GEMM_W_PLAIN 32
 #define CRA5_GEMM_OUT_PLAIN 64
-/* With CRA5_GEMM_HI_ONLY and Kp % 64 == 0 (CRA5_ERR_ARG otherwise): take the wide form - 64-wide k-steps, the
- * summation order of every launch with >= 256 128 x 128 tiles - whatever the problem size.  A slice of such a GEMM
+/* With CRA5_GEMM_HI_ONLY, Kp % 64 == 0 and Kp <= 8192 (CRA5_ERR_ARG otherwise): take the wide form - 64-wide k-steps,
+ * the summation order of every launch with >= 256 128 x 128 tiles - whatever the problem size.  A slice of such a GEMM
  * computed on its own (the rows / columns of a subset decode) then rounds exactly like the big launch; without the flag
  * a smaller problem takes the 32-wide k-step form, whose other summation order rounds differently.  Plain operands are
  * accepted at any size with it. */
@@ -169,6 +173,23 @@ int cra5_gemm_nt_split(const uint16_t *A, int lda_kp, const uint16_t *W, int ldw
                        int ldc, uint16_t *C_split, int ldc_split_kp, const float *bias,
                        const float *res, int ldr, int M, int N, int Kp, float wscale_inv,
                        int flags, void *stream);
+
+/* The form a cra5_gemm_nt_split call of this shape, these flags and these outputs takes - THE rule, evaluated on the
+ * host without a device: the launcher picks its kernel from this answer, and a caller that must name another launch's
+ * form (a slice that promises the whole GEMM's bits) asks here instead of restating it.  CRA5_ERR_ARG: the launcher
+ * refuses the combination.  Otherwise the tile's rows (64 / 128 / 192 / 256, form & CRA5_FORM_TILE) plus
+ *   CRA5_FORM_K64      64-wide k-steps (reduced-precision mode, Kp % 64 == 0 and >= 256 128 x 128 tiles or
+ *                      CRA5_GEMM_WIDE_K); else 32-wide.  Two calls sum a product's K terms in the same order exactly
+ *                      when they agree in this bit (and in HI_ONLY and Kp),
+ *   CRA5_FORM_CHAINED  Kp > 8192 with an fp32 output alone and no GELU: K is cut into chunks of <= 8192 (multiples of
+ *                      64 in reduced-precision mode when Kp is one) that add up through C, every chunk in this form.
+ *                      Any other Kp > 8192 runs one 128-row-tile launch with 32-wide steps,
+ *   CRA5_FORM_PLAIN    plain rows are taken (some CRA5_GEMM_*_PLAIN bit is set: they need CRA5_FORM_K64). */
+#define CRA5_FORM_TILE 0x1c0
+#define CRA5_FORM_K64 1
+#define CRA5_FORM_CHAINED 2
+#define CRA5_FORM_PLAIN 4
+int cra5_gemm_split_form(int M, int N, int Kp, int flags, int has_f32_out, int has_split_out);
 
 
 /* fp32 [rows][K] (row stride ldx) * scale -> split-f16 [rows][2*Kp]. Used once per weight
@@ -205,13 +226,14 @@ int cra5_window_attention_f32(const float *qkv, const float *pad_row, float *out
  * (qkv_kp = 3C) and a split pad row, writing fp32 `out` and/or split-f16 `out_split`.
  * Requires head dim 64 and wh*ww % 32 == 0 (the 576-token windows and the 10 368-token global
  * attention); a window that is not the whole grid must have <= 1152 tokens (CRA5_ERR_ARG otherwise);
- * other shapes use cra5_window_attention_f32.  hi_only != 0: reduced-precision mode
- * (plain f16 q/k/v/p operands, 8 MFMAs per tile instead of 24; fp32 softmax statistics; only the hi plane of
- * out_split is written): 1 = split rows, 3 = PLAIN f16 rows (qkv, the pad row and out_split: element n at half n, row
- * pitches unchanged).  Any other hi_only: CRA5_ERR_ARG. */
+ * other shapes use cra5_window_attention_f32.  mode (the CRA5_GEMM_* mode word): 0, or CRA5_GEMM_HI_ONLY: the
+ * reduced-precision mode (plain f16 q/k/v/p operands, 8 MFMAs per tile instead of 24; fp32 softmax statistics; only the
+ * hi plane of out_split is written) on split rows, or CRA5_GEMM_HI_ONLY | CRA5_GEMM_A_PLAIN | CRA5_GEMM_OUT_PLAIN: that
+ * mode on PLAIN f16 rows (qkv, the pad row and out_split: element n at half n, row pitches unchanged - plain rows in
+ * means plain rows out, and the pad row goes with the input).  Any other mode: CRA5_ERR_ARG. */
 int cra5_window_attention_split(const uint16_t *qkv_split, int qkv_kp, const uint16_t *pad_row_split,
                                 float *out, uint16_t *out_split, int out_kp, int C, int heads,
-                                int H, int W, int wh, int ww, float scale, int hi_only,
+                                int H, int W, int wh, int ww, float scale, int mode,
                                 void *stream);
 
 /* The same call with a caller-owned device workspace.  With it, the whole-grid (global) launch runs the BALANCED
@@ -230,7 +252,7 @@ int cra5_attention_balanced_plan(int n_tokens, int heads, size_t *workspace_byte
 size_t cra5_attention_workspace_bytes(int n_tokens, int heads);
 int cra5_window_attention_split_ws(const uint16_t *qkv_split, int qkv_kp, const uint16_t *pad_row_split,
                                    float *out, uint16_t *out_split, int out_kp, int C, int heads,
-                                   int H, int W, int wh, int ww, float scale, int hi_only,
+                                   int H, int W, int wh, int ww, float scale, int mode,
                                    void *workspace, size_t workspace_bytes, void *stream);
 
 /* Un-embed as ONE fused launch pair (vit_nlc.py:628-630, 666-669: ConvTranspose2d(D -> C, kernel (11, 10), stride
@@ -241,12 +263,15 @@ int cra5_window_attention_split_ws(const uint16_t *qkv_split, int qkv_kp, const 
  * adds the overlap pairs in fixed order: no [tokens][C*110] column matrix, no pass over it, deterministic, and
  * bit-identical to cra5_gemm_nt_split + cra5_col2im_f32.  Only this geometry (kh 11, kw 10, strides 10, W % 4 == 0,
  * Kp <= 8192); cra5_unembed_side_bytes returns 0 and the launcher CRA5_ERR_ARG for anything else - use the two-call
- * form then.  hi_only: the reduced-precision mode of cra5_gemm_nt_split - bit 0 (1) hi-only products, | 2 the A rows are
- * plain f16 rows, | 4 the weight is a packed plain [N][Kp] f16 matrix (bits 1 / 2 only with bit 0; see CRA5_GEMM_A_PLAIN). */
+ * form then.  mode (the CRA5_GEMM_* mode word): 0, or CRA5_GEMM_HI_ONLY with any of CRA5_GEMM_A_PLAIN (the A rows are
+ * plain f16 rows) and CRA5_GEMM_W_PLAIN (the weight is a packed plain [N][Kp] f16 matrix); any other word is
+ * CRA5_ERR_ARG.  The launch is the 256 x 256 tile; with CRA5_GEMM_HI_ONLY it takes the form cra5_gemm_split_form gives
+ * for mode | CRA5_GEMM_WIDE_K - 64-wide k-steps whenever Kp % 64 == 0, which the plain rows need - and 32-wide steps
+ * where that is refused. */
 size_t cra5_unembed_side_bytes(int C, int H, int W, int kh, int kw, int sh, int sw);
 int cra5_gemm_nt_split_unembed(const uint16_t *A, int lda_kp, const uint16_t *W_split, int ldw_kp, float *x,
                                float *side, size_t side_bytes, const float *mean, const float *stdv, int M, int Kp,
-                               float wscale_inv, int C, int H, int W, int kh, int kw, int sh, int sw, int hi_only,
+                               float wscale_inv, int C, int H, int W, int kh, int kw, int sh, int sw, int mode,
                                void *stream);
 
 /* ============================ device: layout / conv edges ===================== */

@@ -158,6 +158,43 @@ def test_gemm_wide_k_slice_equals_the_big_launch(dev):
         assert torch.equal(corner, big[300:556, 1500:1756])
 
 
+@pytest.mark.parametrize("K", [64, 96])
+@pytest.mark.parametrize("M,N", [(1920, 2176), (2048, 2048)])      # 255 and 256 128 x 128 tiles
+def test_launcher_accepts_what_the_form_query_accepts(dev, M, N, K):
+    """Plain operands in the reduced-precision mode, with and without CRA5_GEMM_WIDE_K, on both sides of the tile-count
+    and Kp % 64 thresholds: where ops.gemm_form (cra5_gemm_split_form) refuses, the launcher raises CRA5_ERR_ARG and
+    writes nothing; where it accepts, the launch is the exact hi.hi sum."""
+    from cra5_amd._lib import Cra5Error
+    a, w, sa, sw, pa, pw = _split_operands(M, N, K, dev, M + N + K)
+    e, g, _ = X.three_product_expectation(pa, pw, sw.scale_inv, hi_only=True)
+    ppa, ppw = _plain_rows_of(sa), sw.plain_copy()
+    for wide in (False, True):
+        flags = ops.GEMM_HI_ONLY | ops.GEMM_A_PLAIN | ops.GEMM_W_PLAIN | (ops.GEMM_WIDE_K if wide else 0)
+        form = ops.gemm_form(M, N, sa.Kp, flags, True, False)
+        # plain rows need 64-wide k-steps: Kp % 64 == 0 and (>= 256 tiles or the forced wide form)
+        assert (form >= 0) == (sa.Kp % 64 == 0 and (wide or (M, N) == (2048, 2048))), (M, N, K, wide, form)
+        out = torch.full((M, N), float("nan"), device=dev)
+        if form < 0:
+            assert form == ops.ERR_ARG
+            with pytest.raises(Cra5Error) as ei:
+                ops.gemm_nt_split(ppa, ppw, out=out, hi_only=True, wide_k=wide)
+            assert ei.value.status == ops.ERR_ARG
+            torch.cuda.synchronize()
+            assert bool(torch.isnan(out).all()), (M, N, K, wide)
+        else:
+            assert form & ops.FORM_K64 and form & ops.FORM_PLAIN and not form & ops.FORM_CHAINED
+            assert form & ops.FORM_TILE == 256          # M >= 1024, N >= 2048: the 256-row tile, forced wide or not
+            timer, ops.TIMER = ops.TIMER, ops.KernelTimer()
+            try:
+                ops.gemm_nt_split(ppa, ppw, out=out, hi_only=True, wide_k=wide)
+                booked = ops.TIMER.summary()
+            finally:
+                ops.TIMER = timer
+            X.assert_exact(out, e, g, f"gemm hi_only plain {M}x{N}x{K} wide_k={wide}")
+            # the timer books a launch by the kernel it runs: 255 tiles with CRA5_GEMM_WIDE_K is a big-tile launch
+            assert list(booked) == ["gemm_nt_split"] and booked["gemm_nt_split"]["launches"] == 1
+
+
 # ------------------------------------------------------------------------------------------------ small-M GEMM
 
 

@@ -634,7 +634,7 @@ def test_window_attention_plain_rows_equal_the_hi_only_split_launch(dev, ws):
 def test_split_attention_shape_rule(dev):
     """Windows that are not the whole grid keep a per-block row-offset table: more than
     ops.MAX_WIN_TOKENS tokens per window is refused by the C ABI (the model then uses the exact-f32
-    kernel, ops.split_attention_ok says so beforehand).  So is a hi_only other than 0, 1 or 3."""
+    kernel, ops.split_attention_ok says so beforehand).  So is a mode word other than the three the entry points take."""
     H, W, C, heads = 64, 64, 64, 1
     assert ops.split_attention_ok(C, heads, 32, 32, H, W)           # 1024-token windows: fine
     assert not ops.split_attention_ok(C, heads, 64, 32, H, W)       # 2048-token windows: no
@@ -648,12 +648,19 @@ def test_split_attention_shape_rule(dev):
     ops.window_attention_split(qkv, pad, heads, H, W, 32, 32, out_split=out)
     torch.cuda.synchronize()
     assert torch.isfinite(out.to_float()).all()
-    # hi_only is 0, 1 or 3: any other value (4 once selected a removed windowed schedule) is refused before a launch
+    # the mode word is 0, HI_ONLY or HI_ONLY | A_PLAIN | OUT_PLAIN: any other word is refused before a launch, by both
+    # entry points - 4 (once a removed windowed schedule), plain rows in without plain rows out and the reverse, plain rows
+    # without the reduced-precision mode, a GEMM-only bit, and the codes 1 / 3 the entry points took before the one word
     from cra5_amd import _lib
-    rc = _lib.lib().cra5_window_attention_split(qkv.data.data_ptr(), qkv.Kp, pad.data.data_ptr(), None,
-                                                out.data.data_ptr(), out.Kp, C, heads, H, W, 32, 32, 0.125, 4,
-                                                torch.cuda.current_stream().cuda_stream)
-    assert rc == -7   # CRA5_ERR_ARG
+    HI, A_PL, W_PL, O_PL, WIDE = ops.GEMM_HI_ONLY, ops.GEMM_A_PLAIN, ops.GEMM_W_PLAIN, ops.GEMM_OUT_PLAIN, ops.GEMM_WIDE_K
+    out.data.fill_(0x7e00)   # f16 NaN halves: a launch would overwrite them
+    args = (qkv.data.data_ptr(), qkv.Kp, pad.data.data_ptr(), None, out.data.data_ptr(), out.Kp, C, heads, H, W, 32, 32, 0.125)
+    st = torch.cuda.current_stream().cuda_stream
+    for word in (4, HI | A_PL, HI | O_PL, A_PL | O_PL, HI | A_PL | O_PL | W_PL, HI | WIDE, 1, 3):
+        assert _lib.lib().cra5_window_attention_split(*args, word, st) == -7, word   # CRA5_ERR_ARG
+        assert _lib.lib().cra5_window_attention_split_ws(*args, word, None, 0, st) == -7, word
+    torch.cuda.synchronize()
+    assert bool((out.data == 0x7e00).all())
 
 
 def test_split_f16_range_guard(dev):
