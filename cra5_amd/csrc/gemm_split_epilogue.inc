@@ -50,7 +50,8 @@
           if (Cs && nw < (int)(ldcs >> 1)) {
             unsigned short *sp = Cs + (size_t)m * ldcs + (o_plain ? nw : (nw >> 5) * 64 + (nw & 31));
             *reinterpret_cast<uint2 *>(sp) = make_uint2(0u, 0u);
-            if (!o_plain) *reinterpret_cast<uint2 *>(sp + 32) = make_uint2(0u, 0u);
+            // (reduced-precision mode: no lo half of C_split is written, padding included - include/cra5_amd.h)
+            if (NPROD == 3) *reinterpret_cast<uint2 *>(sp + 32) = make_uint2(0u, 0u);
           }
           continue;
         }

@@ -587,6 +587,9 @@ extern "C" int cra5_gemm_split_form(int M, int N, int Kp, int flags, int has_f32
   // cannot hold; plain-f16 operands / output exist in this form only (the caller falls back to split rows)
   const bool k64 = hi && !longk && Kp % 64 == 0 && (big || force_wide);
   if ((force_wide && (!k64 || chained)) || (plain && !k64)) return CRA5_ERR_ARG;
+  // the one-launch long-K kernel exists as the three-product instantiation alone: it would read both lo planes, sum
+  // hi.lo + lo.hi too and write the lo halves of C_split, whatever the mode word says
+  if (hi && longk) return CRA5_ERR_ARG;
   // measured on MI355X (tools/gemm_bench.py, M = 10368): N = 1024 (proj, fc2, patch-embed): 192x256 tiles = 216 blocks,
   // one round on 256 CUs; N >= 3072: 256x256 tiles.  < 256 128 x 128 tiles: 64 x 64 tiles (launch-bound sizes).
   // (a 4-wave 256 x 256 instantiation - one wave per SIMD, 128 x 128 per wave, 256 accumulator AGPRs, a third less

@@ -328,7 +328,8 @@ def gemm_form(M, N, Kp, flags=0, f32_out=True, split_out=False):
 @functools.lru_cache(maxsize=None)
 def plain_ok(M, N, Kp):
     """Shapes on which cra5_gemm_nt_split takes plain-f16 operands / writes a plain output in the reduced-precision mode
-    (the 64-wide k-step form by the launch's own size; Kp > 8192: the chained call, fp32 output alone)."""
+    (the 64-wide k-step form by the launch's own size; Kp > 8192: the chained call, fp32 output alone - with a split
+    output or a GELU the reduced-precision mode refuses Kp > 8192, plain rows or not)."""
     return gemm_form(M, N, Kp, GEMM_HI_ONLY | GEMM_A_PLAIN | GEMM_W_PLAIN | GEMM_OUT_PLAIN) >= 0
 
 
@@ -356,7 +357,8 @@ def gemm_nt_split(a, w, bias=None, res=None, gelu=False, out=None, out_split=Non
     """epi(a @ w^T) with a, w SplitMat (same K).  out: fp32 [M, N] (row-strided ok) unless
     want_f32=False; out_split: SplitMat [M, N] to receive the split-f16 result.  Reduced-precision mode (hi_only): a / w
     may be PLAIN matrices (SplitMat.plain) and out_plain=True writes out_split's rows plain; wide_k=True takes the
-    64-wide k-step form (CRA5_GEMM_WIDE_K) at any size - the summation order of the big launches this one is a slice of."""
+    64-wide k-step form (CRA5_GEMM_WIDE_K) at any size - the summation order of the big launches this one is a slice of.
+    hi_only with K > 8192 exists as the chained call alone (no out_split, no gelu); otherwise Cra5Error(ERR_ARG)."""
     _dev(a.data, w.data, bias, res, out)
     M, N = a.rows, w.rows
     assert a.Kp == w.Kp and a.K == w.K, (a.K, w.K)

@@ -139,8 +139,10 @@ int cra5_pmf_to_quantized_cdf(const float *pmf, int n, int precision, uint32_t *
  * accepts; any other word is CRA5_ERR_ARG before a launch).
  * CRA5_GEMM_HI_ONLY: reduced-precision mode, hi.hi product only (plain f16 operands, fp32 accumulate, 1 MFMA per
  * product instead of 3) - BASELINE.json configs[4], RMSE-gated.  Only the hi plane of A / W is read, and only the hi
- * plane of C_split is WRITTEN (its lo halves keep whatever they held: a consumer of that matrix must run in this mode
- * too). */
+ * plane of C_split is WRITTEN (its lo halves, those of the pad columns included, keep whatever they held: a consumer of
+ * that matrix must run in this mode too).  Kp > 8192 is taken in the chained form only (an fp32 output alone, no GELU:
+ * CRA5_FORM_CHAINED); with a split output or a GELU it is CRA5_ERR_ARG - the one-launch long-K kernel has no
+ * reduced-precision instantiation. */
 #define CRA5_GEMM_HI_ONLY 8
 /* With CRA5_GEMM_HI_ONLY, where the launch takes 64-wide k-steps (cra5_gemm_split_form; CRA5_ERR_ARG otherwise): the
  * operand / the split output is a PLAIN f16 matrix - a row is its k-values as contiguous halves (`lda_kp` / `ldw_kp` /
@@ -183,7 +185,8 @@ int cra5_gemm_nt_split(const uint16_t *A, int lda_kp, const uint16_t *W, int ldw
  *                      when they agree in this bit (and in HI_ONLY and Kp),
  *   CRA5_FORM_CHAINED  Kp > 8192 with an fp32 output alone and no GELU: K is cut into chunks of <= 8192 (multiples of
  *                      64 in reduced-precision mode when Kp is one) that add up through C, every chunk in this form.
- *                      Any other Kp > 8192 runs one 128-row-tile launch with 32-wide steps,
+ *                      Any other Kp > 8192 runs one 128-row-tile launch with 32-wide steps in the fp32-accurate mode and
+ *                      is CRA5_ERR_ARG with CRA5_GEMM_HI_ONLY,
  *   CRA5_FORM_PLAIN    plain rows are taken (some CRA5_GEMM_*_PLAIN bit is set: they need CRA5_FORM_K64). */
 #define CRA5_FORM_TILE 0x1c0
 #define CRA5_FORM_K64 1

@@ -82,7 +82,7 @@ def launcher_status(L, M, N, Kp, flags, f32_out, split_out):
 
 def test_query_is_the_old_rule_and_the_launcher_refuses_what_it_refuses():
     L = _lib.lib()
-    n_ok = n_refused = n_wide_chained = n_mixed = 0
+    n_ok = n_refused = n_wide_chained = n_mixed = n_hi_longk = 0
     for M, N, Kp in shapes():
         for bits in itertools.product((0, 1), repeat=len(MODE_BITS)):
             mode = sum(b for b, on in zip(MODE_BITS, bits) if on)
@@ -96,6 +96,12 @@ def test_query_is_the_old_rule_and_the_launcher_refuses_what_it_refuses():
                     # others (later flags carry no WIDE bit) - a form no caller can mean.  Now refused.
                     assert not old[3] & WIDE
                     old, n_wide_chained = None, n_wide_chained + 1
+                if old is not None and not old[2] and flags & HI and Kp > 8192:
+                    # THE third change: the old ladder sent every one-launch Kp > 8192 (a split output or a GELU) to the
+                    # three-product long-K kernel whatever the mode word said - both lo planes read, hi.lo + lo.hi summed,
+                    # the lo halves of C_split written.  The reduced-precision mode has no such kernel: now refused.
+                    assert old[:2] == (128, {32}) and (split_out or gelu), case
+                    old, n_hi_longk = None, n_hi_longk + 1
                 if old is None:
                     assert got == ops.ERR_ARG, case
                     assert launcher_status(L, *case) == ops.ERR_ARG, case
@@ -113,7 +119,7 @@ def test_query_is_the_old_rule_and_the_launcher_refuses_what_it_refuses():
                 assert got & ops.FORM_TILE in (64, 128, 192, 256)
                 n_ok += 1
     # the sweep saw every kind of answer
-    assert n_ok > 1000 and n_refused > 1000 and n_wide_chained > 0 and n_mixed > 0
+    assert n_ok > 1000 and n_refused > 1000 and n_wide_chained > 0 and n_mixed > 0 and n_hi_longk > 0
 
 
 def test_production_launches_keep_their_forms():
