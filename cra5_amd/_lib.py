@@ -83,6 +83,9 @@ SIGNATURES = {
     "cra5_zonal_spectrum_slab_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cra5_zonal_spectrum_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                         c_void_p, c_void_p, c_void_p]),
+    "cra5_frame_quantiles_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cra5_frame_quantiles_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_size_t, c_void_p, c_void_p]),
     "cra5_time_accumulate_f32": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cra5_time_finish_f32": (c_int, [c_size_t, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),

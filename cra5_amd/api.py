@@ -772,13 +772,13 @@ class cra5_api:
         return self._decode_batch(time_stamps, paths, 'de_normalized', None, workers, sink, variables, region, stride,
                                   coarsen, residual, pack, what="decode_to_nc", per_variable=True, regrid=regrid)
 
-    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, sel, spectrum=False, tol=None):
+    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, sel, spectrum=False, tol=None, quantiles=None):
         """One frame of evaluate_batch on the calling frame thread: the truth is staged once into this thread's device
         frame buffer; the reconstruction comes from the in-memory strings (bin_path None) or from `bin_path`, and only
         the per-channel statistics leave the device.  sel.coarsen = (k_lat, k_lon): both frames are coarsened on the device
         by the same kernel (the reconstruction inside its decode, the truth by VAEformer.coarsen_frame) and compared on
         the coarse grid; sel.regrid likewise (VAEformer.regrid_frame), on the target grid.  spectrum: the zonal power
-        spectra of the same device pair join the report."""
+        spectra of the same device pair join the report; quantiles (validated probabilities): its exact quantiles too."""
         from . import metrics
         if bin_path is None:
             enc, x = self._encode_staged(ts, arr, save_root, write=save_root is not None)
@@ -824,6 +824,10 @@ class cra5_api:
                 t_s = time.perf_counter()
                 spec = metrics.zonal_spectrum(x_hat, x, lat_weights=lat_weights)
                 self._log("spectrum", t_s)
+            if quantiles is not None:
+                t_q = time.perf_counter()
+                quant = metrics.frame_quantiles(x_hat, x, quantiles, lat_weights=lat_weights)
+                self._log("quantiles", t_q)
         std = self._std_flat.detach().cpu().numpy().astype(np.float64)
         rep = dict(time_stamp=ts, variables=list(sel.names))
         rep.update(err)
@@ -831,6 +835,9 @@ class cra5_api:
         if spectrum:
             rep.update({k: spec[k] for k in ("wavenumber", "power_truth", "power_recon", "power_error",
                                              "resolved_wavenumber")})
+        if quantiles is not None:
+            rep.update({k: quant[k] for k in ("quantile", "quantile_truth", "quantile_recon", "quantile_abs_error",
+                                              "quantile_shift")})
         rep["bin_bytes"] = n_bytes
         rep["compression_ratio"] = C * H * W * 4 / n_bytes
         if side is not None:
@@ -839,7 +846,7 @@ class cra5_api:
         return rep
 
     def evaluate_batch(self, time_stamps, data=None, bins=None, save_root=None, workers=12, lat_weights="era5",
-                       coarsen=None, spectrum=False, max_error=None, regrid=None):
+                       coarsen=None, spectrum=False, max_error=None, regrid=None, quantiles=None):
         """Per-variable reconstruction error of many frames, through the frame pipeline, without copying any
         reconstruction to the host.  Truth frames: `data` (a matching list of host arrays / tensors, physical units) or
         the NetCDF files of `time_stamps`.
@@ -864,6 +871,11 @@ class cra5_api:
         pair (with coarsen=, the coarse pair): wavenumber int64 [K], power_truth / power_recon / power_error float64
         [C, K] and resolved_wavenumber int64 [C]; only the spectra leave the device.  The compared width (W, or the coarse
         Wo) must have no prime factor above 5.
+        quantiles=(p, ...): 1 to 16 probabilities in [0, 1] - every report also carries the exact quantiles of
+        metrics.frame_quantiles on the same device pair (after the max_error correction; with coarsen= / regrid= the coarse
+        or target pair, under the lat_weights resolved there, as integer row weights): quantile float64 [Q], quantile_truth /
+        quantile_recon / quantile_abs_error / quantile_shift float64 [C, Q]; only the quantiles leave the device.  A bad
+        `quantiles` raises before any frame is touched.
         max_error (encode_era5_as_bin; not with coarsen=): the tuning tool of the residual layer - the reconstruction is
         corrected on the device before the metric and the spectrum, as a decode with the sidecar would see it, and every
         report gains res_bytes (the sidecar's size), records, escapes, tol and compression_ratio_total = C * H * W * 4 /
@@ -892,13 +904,18 @@ class cra5_api:
             if not ops.spectrum_width_ok(Wc):
                 raise ValueError(f"evaluate_batch(spectrum=True): the compared width {Wc} is not supported - the row "
                                  f"transform takes 2 <= W <= {ops.SPECTRUM_MAX_W} with no prime factor above 5")
+        if quantiles is not None:
+            from . import metrics
+            Hc, Wc = sel.shape[-2:]
+            # validated, computed and uploaded once, here: the frame threads find weights and targets in metrics' cache
+            quantiles = tuple(metrics.quantile_plan(quantiles, lat_weights, Hc, Wc, self.mean.device)[2].tolist())
         n = len(time_stamps)
         frames = list(data) if data is not None else [None] * n
         if len(frames) != n or (bins is not None and len(bins) != n):
             raise ValueError("evaluate_batch: time_stamps, data and bins must have the same length")
         paths = list(bins) if bins is not None else [None] * n
         reps = self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights, sel,
-                                                                         bool(spectrum), tol),
+                                                                         bool(spectrum), tol, quantiles),
                                            list(zip(time_stamps, frames, paths)))
         for r in reps:
             r.update(extra)

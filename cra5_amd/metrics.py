@@ -133,3 +133,113 @@ def zonal_spectrum(x_hat, x, lat_weights="era5"):
     p, nf = r[:3 * C * K].reshape(3, C, K), r[3 * C * K:].astype(np.int64)
     return dict(wavenumber=np.arange(K, dtype=np.int64), power_truth=p[0].copy(), power_recon=p[1].copy(),
                 power_error=p[2].copy(), resolved_wavenumber=resolved_wavenumber(p[0], p[2], nf), nonfinite=nf)
+
+
+# ---- exact quantiles (csrc/quantile.hip) ----------------------------------------------------------------------------------
+# Per channel three fields - truth x, recon x_hat, abs_error |x_hat - x| (the metric's fp32 difference) - and integer row
+# weights w_h = rint(float64 L(h) * 2^16) (None: 1; a row of weight 0 does not count).  Wtot = W * sum_h w_h, and for a
+# probability p the target T(p) = min(Wtot, max(1, ceil(p * float(Wtot)))), in float64, the product rounded once.
+# Q_f(c, p) = the smallest value v of field f in channel c whose points with value <= v weigh >= T(p): an element of the
+# field with its own fp32 bits, nothing interpolated; numpy's "inverted_cdf" when all weights are 1.
+
+QUANTILE_WEIGHT_ONE = 1 << 16     # the integer weight of L(h) = 1
+QUANTILE_WEIGHT_MAX = 1 << 20     # cra5_frame_quantiles_f32's limit per row
+_QUANTILE_CACHE = {}              # (weights identity, H, W, q, device) -> (keep-alive, row_w dev, targets dev, q array)
+_QUANTILE_CACHE_MAX = 64
+
+
+def quantile_weights(lat_weights, H):
+    """The integer row weights of the quantiles, int64 [H]: ones for None, else rint(float64 L(h) * 2^16) of "era5"
+    (latitude_weights(H)) or of an [H] array.  ValueError for a negative or non-finite weight, a weight above 2^20
+    (L(h) > 16) and for weights that are all 0."""
+    H = int(H)
+    if lat_weights is None:
+        return np.ones(H, dtype=np.int64)
+    if isinstance(lat_weights, str):
+        if lat_weights != "era5":
+            raise ValueError(f"lat_weights must be 'era5', None or an [H] array (got {lat_weights!r})")
+        L = latitude_weights(H)
+    else:
+        L = lat_weights.detach().cpu().numpy() if isinstance(lat_weights, torch.Tensor) else np.asarray(lat_weights)
+        if L.shape != (H,):
+            raise ValueError(f"lat_weights must have shape [{H}] (got {tuple(L.shape)})")
+        L = L.astype(np.float64)
+    if not np.all(np.isfinite(L)) or np.any(L < 0):
+        raise ValueError("quantile weights must be finite and >= 0")
+    w = np.rint(L * float(QUANTILE_WEIGHT_ONE))
+    if np.any(w > QUANTILE_WEIGHT_MAX):
+        raise ValueError(f"quantile weights: rint(L(h) * 2^16) must not exceed 2^20 = {QUANTILE_WEIGHT_MAX} "
+                         f"(L(h) <= 16; got max L = {float(L.max()):g})")
+    w = w.astype(np.int64)
+    if not np.any(w > 0):
+        raise ValueError("quantile weights: every row has integer weight 0 - nothing to count")
+    return w
+
+
+def quantile_targets(q, row_w, W):
+    """The integer targets T(p) of the probabilities `q` under the integer row weights `row_w` [H] and the width W, int64
+    [Q] in the order given (duplicates allowed).  ValueError unless q is a non-empty sequence of at most 16 finite floats
+    in [0, 1]."""
+    from .ops import QUANTILE_MAX_Q
+    if isinstance(q, (str, bytes)) or not hasattr(q, "__len__") or np.ndim(q) != 1:
+        raise ValueError(f"quantiles must be a sequence of 1 to {QUANTILE_MAX_Q} probabilities in [0, 1] (got {q!r})")
+    n = len(q)
+    if not 1 <= n <= QUANTILE_MAX_Q:
+        raise ValueError(f"quantiles must be a sequence of 1 to {QUANTILE_MAX_Q} probabilities in [0, 1] (got {n})")
+    try:
+        p = np.array([float(v) for v in q], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"quantiles must be a sequence of 1 to {QUANTILE_MAX_Q} probabilities in [0, 1] (got {q!r})")
+    if not np.all(np.isfinite(p)) or np.any(p < 0.0) or np.any(p > 1.0):
+        raise ValueError(f"quantiles must be finite probabilities in [0, 1], at most {QUANTILE_MAX_Q} of them "
+                         f"(got {p.tolist()})")
+    wtot = int(W) * int(np.asarray(row_w, dtype=np.int64).sum())
+    if not 1 <= wtot < 1 << 53:
+        raise ValueError(f"quantiles: the total weight W * sum(row_w) = {wtot} must be in 1 .. 2^53 - 1")
+    t = np.ceil(p * float(wtot))                 # float64: the product rounds once
+    return np.minimum(wtot, np.maximum(1, t.astype(np.int64))).astype(np.int64)
+
+
+def quantile_plan(q, lat_weights, H, W, device):
+    """(row_w device int32 [H] or None, targets device int64 [Q], q float64 [Q]) - validated, and cached per (weights
+    identity, H, W, q, device), so that a batch uploads them once."""
+    try:
+        qkey = tuple(float(v) for v in q)
+    except (TypeError, ValueError):
+        qkey = None
+    wkey = lat_weights if lat_weights is None or isinstance(lat_weights, str) else id(lat_weights)
+    key = (wkey, int(H), int(W), qkey, str(device))
+    hit = _QUANTILE_CACHE.get(key) if qkey is not None else None
+    if hit is not None:
+        return hit[1:]
+    w = quantile_weights(lat_weights, H)
+    t = quantile_targets(q, w, W)
+    row_w = None if lat_weights is None else torch.from_numpy(w.astype(np.int32)).to(device)
+    plan = (lat_weights, row_w, torch.from_numpy(t).to(device), np.array(qkey, dtype=np.float64))
+    if len(_QUANTILE_CACHE) >= _QUANTILE_CACHE_MAX:
+        _QUANTILE_CACHE.clear()
+    _QUANTILE_CACHE[key] = plan        # (holds lat_weights: its id cannot be reused while the entry lives)
+    return plan[1:]
+
+
+def frame_quantiles(x_hat, x, q, lat_weights="era5"):
+    """Exact quantiles of the truth `x`, the reconstruction `x_hat` and the error magnitude |x_hat - x|, per channel:
+    device fp32 tensors [C, H, W] or [1, C, H, W] of the same shape; q: 1 to 16 probabilities in [0, 1], any order;
+    lat_weights as reconstruction_error ("era5", None or an [H] array), turned into integer row weights by
+    quantile_weights - with weights the quantiles are area-true, a row of weight 0 (the poles) does not count.  Four
+    streaming digit passes on the GPU (ops.frame_quantiles, the current stream); only 3 x C x Q numbers come back, each an
+    element of its field with its own fp32 bits (with lat_weights=None: np.quantile(..., method="inverted_cdf")).
+    Returns {"quantile": float64 [Q] (q as given), "quantile_truth", "quantile_recon", "quantile_abs_error": float64
+    [C, Q], "quantile_shift" = quantile_recon - quantile_truth (negative at p = 0.9999: the upper tail was damped),
+    "nonfinite": int64 [C]}; a channel with nonfinite > 0 has NaN in every quantile."""
+    x_hat, x = _frame_pair("frame_quantiles", x_hat, x)
+    from . import ops
+    C, H, W = x.shape
+    row_w, targets, qa = quantile_plan(q, lat_weights, H, W, x.device)
+    Q = len(qa)
+    out = torch.empty((3 * C * Q + C,), device=x.device, dtype=torch.float64)
+    ops.frame_quantiles(x_hat, x, row_w, targets, out=out)
+    r = out.cpu().numpy()      # the quantiles and the counts: one copy
+    v, nf = r[:3 * C * Q].reshape(3, C, Q), r[3 * C * Q:].astype(np.int64)
+    return dict(quantile=qa.copy(), quantile_truth=v[0].copy(), quantile_recon=v[1].copy(),
+                quantile_abs_error=v[2].copy(), quantile_shift=v[1] - v[0], nonfinite=nf)

@@ -916,6 +916,51 @@ def zonal_spectrum(x_hat, x, lat_w=None, out=None):
     return power, nonfinite
 
 
+QUANTILE_FIELDS = ("truth", "recon", "abs_error")   # the order of the [C, Q] blocks cra5_frame_quantiles_f32 writes
+QUANTILE_MAX_Q = 16                                 # CRA5_QUANTILE_MAX_Q
+
+
+def frame_quantiles(x_hat, x, row_w, targets, out=None):
+    """cra5_frame_quantiles_f32: exact quantiles of the truth x, the reconstruction x_hat and |x_hat - x| (both contiguous
+    fp32 device tensors [C, H, W]).  row_w: contiguous int32 device [H] of integer row weights in 0 .. 2^20, or None = all
+    1; targets: contiguous int64 device [Q], 1 <= Q <= QUANTILE_MAX_Q, every entry in 1 .. W * sum(row_w) (the caller's
+    duty: metrics.quantile_weights / quantile_targets) -> (quantiles, nonfinite): fp64 device tensors [3, C, Q] (in the
+    order of QUANTILE_FIELDS, every fp32 result widened exactly) and [C], both views of `out`, one flat fp64 device tensor
+    of 3 * C * Q + C elements (allocated when None), so that one copy brings everything to the host.  On the current
+    stream; the workspace comes from torch's caching allocator and is initialised by the launcher."""
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+               for t in (x_hat, x)):
+        raise TypeError("frame_quantiles takes contiguous fp32 device tensors")
+    if x_hat.dim() != 3 or tuple(x_hat.shape) != tuple(x.shape) or x_hat.device != x.device:
+        raise ValueError(f"frame_quantiles: x_hat {tuple(x_hat.shape)} and x {tuple(x.shape)} must be [C, H, W] of one "
+                         "shape on one device")
+    C, H, W = x.shape
+    if row_w is not None:
+        if not (isinstance(row_w, torch.Tensor) and row_w.is_cuda and row_w.dtype == torch.int32 and row_w.is_contiguous()):
+            raise TypeError("frame_quantiles: row_w must be a contiguous int32 device tensor or None")
+        if tuple(row_w.shape) != (H,) or row_w.device != x.device:
+            raise ValueError(f"frame_quantiles: row_w must be [{H}] on the frames' device")
+    if not (isinstance(targets, torch.Tensor) and targets.is_cuda and targets.dtype == torch.int64
+            and targets.is_contiguous()):
+        raise TypeError("frame_quantiles: targets must be a contiguous int64 device tensor [Q]")
+    if targets.dim() != 1 or not 1 <= targets.shape[0] <= QUANTILE_MAX_Q or targets.device != x.device:
+        raise ValueError(f"frame_quantiles: targets must be [Q] with 1 <= Q <= {QUANTILE_MAX_Q} on the frames' device "
+                         f"(got {tuple(targets.shape)} on {targets.device})")
+    Q = int(targets.shape[0])
+    nb = lib().cra5_frame_quantiles_ws_bytes(C, H, W, Q)
+    if nb == 0:
+        raise ValueError(f"frame_quantiles: unsupported frame shape {(C, H, W)}")
+    if out is None:
+        out = torch.empty((3 * C * Q + C,), device=x.device, dtype=torch.float64)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+              and tuple(out.shape) == (3 * C * Q + C,) and out.device == x.device):
+        raise TypeError(f"frame_quantiles: out must be a contiguous fp64 tensor [{3 * C * Q + C}] on the frames' device")
+    ws = torch.empty((nb // 8,), device=x.device, dtype=torch.int64)
+    check(lib().cra5_frame_quantiles_f32(_p(x_hat), _p(x), C, H, W, _p(row_w), _p(targets), Q, _p(ws), nb, _p(out),
+                                         _stream()), "cra5_frame_quantiles_f32")
+    return out[:3 * C * Q].view(3, C, Q), out[3 * C * Q:]
+
+
 RESIDUAL_SPAN = 4096     # CRA5_RESIDUAL_SPAN
 RESIDUAL_MAX_TOL = 1e30  # step = 2 * tol must stay finite in fp32
 

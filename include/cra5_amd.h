@@ -450,6 +450,25 @@ int cra5_zonal_spectrum_f32(const float *x_hat, const float *x, int C, int H, in
                             const double *twiddle, double *slab, size_t slab_bytes, double *out, double *nonfinite,
                             void *stream);
 
+/* Exact quantiles of a frame pair (csrc/quantile.hip; DESIGN.md section 4, "Quantiles"): x_hat, x [C][H][W] fp32, 4-byte
+ * aligned.  Per channel three fields: truth x, recon x_hat, abs_error |x_hat - x| (the fp32 difference of the metric).
+ * row_w: device uint32 [H], the integer weight of every row (<= 2^20; a row of weight 0 does not count), or NULL = all 1.
+ * targets: device uint64 [Q], 1 <= targets[q] <= W * sum_h row_w[h] (the caller's duty).  Q_f(c, q) = the smallest value v
+ * of field f in channel c for which the summed weight of the points with value <= v reaches targets[q]: an element of the
+ * field with its own fp32 bits (-0 and +0 are one value, the sign of a returned zero is unspecified), nothing interpolated.
+ * out, device fp64 [3 * C * Q + C]: the three [C][Q] blocks in the order truth, recon, abs_error, every fp32 result
+ * widened exactly, then the [C] counts of points where x or x_hat is NaN / +-inf (as CRA5_RECON_NONFINITE); a channel
+ * with such a point has NaN in all its 3 * Q results, the other channels are unaffected.  `ws`: caller-owned device
+ * scratch of >= cra5_frame_quantiles_ws_bytes(C, H, W, Q) bytes, 8-byte aligned; the launcher initialises it on `stream`.
+ * Nine launches on `stream` (init, then four 8-bit digit passes of count + select); all counting is in unsigned integers,
+ * so the result is bit-identical from run to run.  ws_bytes returns 0 for bad dimensions (C, H, W < 1, H * W >= 2^31, Q
+ * outside 1 .. CRA5_QUANTILE_MAX_Q); the launcher returns CRA5_ERR_ARG, before any device work, for those, for NULL
+ * pointers (row_w may be NULL), a misaligned or short workspace. */
+#define CRA5_QUANTILE_MAX_Q 16
+size_t cra5_frame_quantiles_ws_bytes(int C, int H, int W, int Q);
+int cra5_frame_quantiles_f32(const float *x_hat, const float *x, int C, int H, int W, const uint32_t *row_w,
+                             const uint64_t *targets, int Q, void *ws, size_t ws_bytes, double *out, void *stream);
+
 /* Per-grid-point statistics over many frames (csrc/timestats.hip): flat fp32 frames x of n elements, accumulators of the
  * same n elements - sum / sumsq fp64, mn / mx fp32.  Each accumulator pointer may be NULL (that statistic is not kept: it
  * is neither read nor written); at least one is given.  Per element i, v = (double)x[i]:
