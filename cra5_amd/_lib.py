@@ -80,6 +80,7 @@ SIGNATURES = {
     "cra5_pack_range_slab_bytes": (c_size_t, [c_int, c_size_t]),
     "cra5_pack_range_f32": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "cra5_pack_i16_f32": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "cra5_unpack_i16_f32": (c_int, [c_void_p, c_int, c_size_t, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
     "cra5_zonal_spectrum_slab_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cra5_zonal_spectrum_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                         c_void_p, c_void_p, c_void_p]),

@@ -205,12 +205,88 @@ class cra5_api:
             sclose()
         return np.concatenate(one_step, 0).astype(np.float32, copy=False)
 
+    INGEST = ("host", "packed", "auto")
+
+    def _ingest_arg(self, ingest):
+        if ingest not in self.INGEST:
+            raise ValueError(f"ingest must be one of {self.INGEST}, got {ingest!r}")
+        return ingest
+
+    def _ingest(self, time_stamp, ingest="host"):
+        """data=None of the encode entry points -> the frame of the time stamp's NetCDF files.  "host": the float32 array of
+        read_data_from_nc; "packed": the files' own int16 codes as a pack.PackedFrame over their mappings, marked
+        `transient` (_stage_packed / _frame close it once its codes have left the mappings), ValueError naming the file
+        and the reason when they do not hold plain packed int16; "auto": packed where possible, else the host route."""
+        if ingest == "host":
+            return self.read_data_from_nc(time_stamp)
+        reason = []
+        frame = _pk.read_era5_nc_packed(self.local_root, time_stamp, self.vnames, self.pressure_level, reason=reason)
+        if frame is not None:
+            frame.transient = True
+            return frame
+        if ingest == "packed":
+            raise ValueError(f"ingest='packed': {reason[0] if reason else time_stamp}")
+        return self.read_data_from_nc(time_stamp)
+
+    def _stage_packed(self, frame, threads=None):
+        """pack.PackedFrame -> the fp32 frame in this thread's device frame buffer (api_x_dev), on the current stream: every
+        block of codes goes from where it lies (a file mapping) into this thread's pinned int16 buffer and on into this
+        thread's int16 device buffer - bytes, half those of the fp32 frame, in ONE turn on the link -, the [C, 4] table
+        follows, and csrc/pack.hip's unpack kernel writes the frame.  As _stage_in copies a float32 frame: with a team
+        (threads > 1) ops.copy_h2d_staged overlaps the host memcpy with the DMA inside the turn; with one thread the memcpy
+        runs on this thread BEFORE its turn (the frame threads copy side by side) and the turn is the DMA alone.
+        A `transient` frame (_ingest) is closed once its codes have left the mappings."""
+        net = self.net
+        threads = threads or self.runtime.copy_threads
+        t0 = time.perf_counter()
+        try:
+            shape = tuple(frame.shape)
+            pin = net._pinned("api_q_in", shape, torch.int16)
+            qdev = net._buf("api_q_in_dev", shape, torch.int16)
+            tpin = net._pinned("api_unpack_table_in", (shape[0], len(ops.UNPACK_FIELDS)), torch.float64)
+            table = net._buf("api_unpack_table", (shape[0], len(ops.UNPACK_FIELDS)), torch.float64)
+            np.copyto(tpin.numpy(), frame.table())
+            swapped = frame.swapped
+            if threads > 1:
+                with self._link("h2d"):
+                    c = 0
+                    for blk in frame.blocks:
+                        ops.copy_h2d_staged(qdev[c:c + blk.shape[0]], blk, pin, threads=threads)
+                        c += blk.shape[0]
+                    table.copy_(tpin, non_blocking=True)
+            else:
+                host = pin.numpy().view(frame.blocks[0].dtype)      # (the blocks' byte order: a plain memcpy)
+                c = 0
+                for blk in frame.blocks:
+                    np.copyto(host[c:c + blk.shape[0]], blk)
+                    c += blk.shape[0]
+                self._log("stage_in_memcpy", t0)
+                with self._link("h2d"):
+                    qdev.copy_(pin, non_blocking=True)              # async H2D on this frame's stream
+                    table.copy_(tpin, non_blocking=True)
+                    if self.link_serial:
+                        torch.cuda.current_stream().synchronize()   # the gate is held until the codes have landed
+            blk = None      # (no view of a mapping outlives close())
+        finally:
+            if frame.transient:
+                frame.close()
+        return ops.unpack_i16(qdev, table, swapped=swapped, out=net._buf("api_x_dev", shape))
+
     def _frame(self, time_stamp, data):
         """-> the frame as a float32 device tensor.  Host arrays go through this thread's pinned staging buffer
         into this thread's persistent device frame buffer (chunked, host memcpy overlapped with the DMA): the
-        returned tensor is that buffer, valid until this thread's next call."""
+        returned tensor is that buffer, valid until this thread's next call.  A pack.PackedFrame crosses as int16 codes
+        and is unpacked on the device (_stage_packed)."""
         if data is None:
             data = self.read_data_from_nc(time_stamp)
+        if isinstance(data, _pk.PackedFrame):
+            if self.net.device.type != "cuda":
+                try:
+                    return torch.from_numpy(_pk.unpack_f32(data)).to(self.device)
+                finally:
+                    if data.transient:
+                        data.close()
+            return self._stage_packed(data)
         if isinstance(data, torch.Tensor):
             if data.is_cuda or not self.net.device.type == "cuda":
                 return data.to(self.device, dtype=torch.float32)
@@ -338,8 +414,11 @@ class cra5_api:
                 binfmt.write_bin(f, output["strings"], output["z_shape"])
         return path
 
-    def encode_to_latent(self, time_stamp=None, save_root=None, latent_type='float', data=None):
-        """cra5_api.py:53-71."""
+    def encode_to_latent(self, time_stamp=None, save_root=None, latent_type='float', data=None, ingest="host"):
+        """cra5_api.py:53-71.  data: a host array / tensor or a pack.PackedFrame; ingest (with data=None): how the NetCDF
+        files are read - "host" | "packed" | "auto" (encode_era5_as_bin)."""
+        if data is None and self._ingest_arg(ingest) != "host":
+            data = self._ingest(time_stamp, ingest)
         frame = self._frame(time_stamp, data)
         with torch.no_grad():
             y = self._checked(frame, lambda: self._encode_y(frame))
@@ -355,8 +434,15 @@ class cra5_api:
             return self.net.compress_from_latent(y)
 
     def encode_era5_as_bin(self, time_stamp, save_root=None, return_format='bin', data=None, max_error=None,
-                           max_fraction=0.25):
-        """cra5_api.py:81-125.  max_error (a positive number: that bound in normalised units on every channel | a dict
+                           max_fraction=0.25, ingest="host"):
+        """cra5_api.py:81-125.  data: a float32 host array / tensor in physical units, or a pack.PackedFrame - int16 codes
+        with their scale_factor / add_offset / fill code: the codes cross the host link, half the bytes, and are unpacked
+        on the GPU to the very bits the host unpacking gives ("Packed int16 input"), so the .bin is
+        byte-identical; a fill code is a NaN and raises the non-finite-input ValueError.  ingest (with data=None): "host"
+        (default) - read_data_from_nc unpacks the NetCDF files on the host; "packed" - the files' int16 codes are staged
+        straight from their mappings (pack.read_era5_nc_packed), ValueError naming the file and the reason when they are
+        not plain packed int16 NetCDF-3; "auto" - packed where possible, else the host route.
+        max_error (a positive number: that bound in normalised units on every channel | a dict
         {variable: bound in physical units}; residual.resolve_tolerance): the frame's own decode is corrected against the
         staged truth on the GPU and the corrections are written beside the unchanged .bin as {save_root}/{yyyy}/{ts}.res -
         decode with residual=True and every point of the corrected channels is within its bound (DESIGN.md section 4,
@@ -369,8 +455,10 @@ class cra5_api:
                 raise ValueError(f"encode_era5_as_bin: max_error writes a sidecar beside the .bin; return_format="
                                  f"{return_format!r} writes none")
             return self.encode_to_latent(time_stamp, latent_type='float' if return_format == 'latent' else 'quantized',
-                                         data=data)
+                                         data=data, ingest=ingest)
         st1 = time.time()
+        if data is None and self._ingest_arg(ingest) != "host":
+            data = self._ingest(time_stamp, ingest)
         frame = self._frame(time_stamp, data)
         st2 = time.time()
         with torch.no_grad():
@@ -468,8 +556,10 @@ class cra5_api:
 
     def _stage_in(self, arr):
         """host array (numpy / CPU tensor, physical units) -> this thread's device frame buffer, through
-        this thread's pinned staging buffer, on the current stream."""
+        this thread's pinned staging buffer, on the current stream.  A pack.PackedFrame: _stage_packed."""
         net = self.net
+        if isinstance(arr, _pk.PackedFrame):
+            return self._stage_packed(arr, threads=max(1, self.batch_copy_threads))
         if isinstance(arr, torch.Tensor):
             if arr.is_cuda:
                 return arr.to(torch.float32)
@@ -514,10 +604,10 @@ class cra5_api:
                 self.phase_log.append((threading.get_ident(), direction + "_wait", t0, t1))
                 self.phase_log.append((threading.get_ident(), direction, t1, time.perf_counter()))
 
-    def _encode_one(self, ts, arr, save_root, write=True, tol=None, max_fraction=None):
+    def _encode_one(self, ts, arr, save_root, write=True, tol=None, max_fraction=None, ingest="host"):
         """One frame of the batch encode on the calling frame thread (its stream, its pinned / device buffers).  tol
         (float32 [C], _residual_tol): the thread then decodes its own strings and writes the residual sidecar."""
-        enc, x = self._encode_staged(ts, arr, save_root, write)
+        enc, x = self._encode_staged(ts, arr, save_root, write, ingest)
         if tol is not None:
             t0 = time.time()
             with torch.no_grad():
@@ -526,12 +616,12 @@ class cra5_api:
             enc["encoding_time"] += time.time() - t0
         return enc
 
-    def _encode_staged(self, ts, arr, save_root, write=True):
+    def _encode_staged(self, ts, arr, save_root, write=True, ingest="host"):
         """_encode_one -> (its dict, the frame on the device: this thread's staged copy, which the compress path only
         reads)."""
         t0 = time.time()
         if arr is None:
-            arr = self.read_data_from_nc(ts)
+            arr = self._ingest(ts, ingest)
         t1 = time.time()
         with torch.no_grad():
             x = self._stage_in(arr)
@@ -549,17 +639,21 @@ class cra5_api:
                     save_path=file_url), x
 
     def encode_era5_batch(self, time_stamps, data=None, save_root=None, workers=12, write=True, max_error=None,
-                          max_fraction=0.25):
-        """encode_era5_as_bin for many time stamps (`data`: matching list of host arrays, or None to read
-        the NetCDF files).  Returns the list of per-frame dicts (same keys as encode_era5_as_bin).
+                          max_fraction=0.25, ingest="host"):
+        """encode_era5_as_bin for many time stamps (`data`: matching list of host arrays or pack.PackedFrame, or None to
+        read the NetCDF files - ingest "host" | "packed" | "auto" as in encode_era5_as_bin: with "packed" every frame
+        thread stages its files' int16 codes straight from their mappings).  Returns the list of per-frame dicts (same
+        keys as encode_era5_as_bin).
         max_error / max_fraction (encode_era5_as_bin): after the compress phase every frame thread decodes its own
         strings, quantises the residual against the staged truth on the GPU and writes {ts}.res beside the (byte-identical)
         {ts}.bin; a frame over the budget ends the call with ResidualBudgetError."""
         save_root = save_root or self.local_root
         self.net._require_gpu()
         tol = self._residual_tol(max_error)
+        self._ingest_arg(ingest)
         frames = list(data) if data is not None else [None] * len(time_stamps)
-        return self._pipeline(workers).map(lambda it: self._encode_one(it[0], it[1], save_root, write, tol, max_fraction),
+        return self._pipeline(workers).map(lambda it: self._encode_one(it[0], it[1], save_root, write, tol, max_fraction,
+                                                                       ingest),
                                            list(zip(time_stamps, frames)))
 
     def _read_frame(self, path, res_path=None):
@@ -679,13 +773,15 @@ class cra5_api:
                              f" (got {type(out).__name__} {getattr(out, 'dtype', None)} {getattr(out, 'shape', None)})")
 
     def roundtrip_batch(self, time_stamps, data=None, save_root=None, workers=12, sink=None, out=None,
-                        return_format='de_normalized'):
+                        return_format='de_normalized', ingest="host"):
         """The reference's test.py loop (test.py:14-59: encode_era5_as_bin then decode_from_bin per time stamp) as a
         STREAM: every frame goes host array -> H2D -> g_a -> rANS -> .bin on disk -> .bin read -> rANS -> g_s -> D2H ->
         `sink(i, frame)` / `out[i]`, `workers` frames in flight - the H2D of one frame, the D2H of another and the GPU /
-        rANS phases of the rest overlap.  Returns [(encode dict, sink's value | host array), ...]."""
+        rANS phases of the rest overlap.  Returns [(encode dict, sink's value | host array), ...].  data items may be
+        pack.PackedFrame; ingest (with data=None): as in encode_era5_as_bin."""
         save_root = save_root or self.local_root
         denorm = self._denorm_arg(return_format)
+        self._ingest_arg(ingest)
         self.net._require_gpu()
         sel = self._select()
         self._check_out(out, len(time_stamps), sel.shape)
@@ -693,7 +789,7 @@ class cra5_api:
 
         def one(item):
             i, ts, arr = item
-            enc = self._encode_one(ts, arr, save_root, True)
+            enc = self._encode_one(ts, arr, save_root, True, ingest=ingest)
             return enc, self._decode_one(i, enc["save_path"], denorm, sel, out, sink)
         return self._pipeline(workers).map(one, [(i, ts, a) for i, (ts, a) in enumerate(zip(time_stamps, frames))])
 
@@ -772,7 +868,8 @@ class cra5_api:
         return self._decode_batch(time_stamps, paths, 'de_normalized', None, workers, sink, variables, region, stride,
                                   coarsen, residual, pack, what="decode_to_nc", per_variable=True, regrid=regrid)
 
-    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, sel, spectrum=False, tol=None, quantiles=None):
+    def _evaluate_one(self, ts, arr, bin_path, save_root, lat_weights, sel, spectrum=False, tol=None, quantiles=None,
+                      ingest="host"):
         """One frame of evaluate_batch on the calling frame thread: the truth is staged once into this thread's device
         frame buffer; the reconstruction comes from the in-memory strings (bin_path None) or from `bin_path`, and only
         the per-channel statistics leave the device.  sel.coarsen = (k_lat, k_lon): both frames are coarsened on the device
@@ -781,12 +878,12 @@ class cra5_api:
         spectra of the same device pair join the report; quantiles (validated probabilities): its exact quantiles too."""
         from . import metrics
         if bin_path is None:
-            enc, x = self._encode_staged(ts, arr, save_root, write=save_root is not None)
+            enc, x = self._encode_staged(ts, arr, save_root, write=save_root is not None, ingest=ingest)
             strings, shape = enc["output"]["strings"], enc["output"]["z_shape"]
             n_bytes = 12 + sum(4 + len(s[0]) for s in strings)     # the .bin container (binfmt.write_bin)
         else:
             if arr is None:
-                arr = self.read_data_from_nc(ts)
+                arr = self._ingest(ts, ingest)
             with open(bin_path, "rb") as f:
                 blob = f.read()
             strings, shape = binfmt.unpack_bin(blob)
@@ -846,7 +943,7 @@ class cra5_api:
         return rep
 
     def evaluate_batch(self, time_stamps, data=None, bins=None, save_root=None, workers=12, lat_weights="era5",
-                       coarsen=None, spectrum=False, max_error=None, regrid=None, quantiles=None):
+                       coarsen=None, spectrum=False, max_error=None, regrid=None, quantiles=None, ingest="host"):
         """Per-variable reconstruction error of many frames, through the frame pipeline, without copying any
         reconstruction to the host.  Truth frames: `data` (a matching list of host arrays / tensors, physical units) or
         the NetCDF files of `time_stamps`.
@@ -854,6 +951,8 @@ class cra5_api:
             written to {save_root}/{yyyy}/{ts}.bin (the bytes encode_era5_as_bin writes) only when save_root is given.
           bins=[paths]: dataset check - the existing .bin files (e.g. downloaded CRA5 files) are decoded and compared with
             the matching truth frames (a truth frame with NaN / inf is reported through `nonfinite`, not refused).
+        A truth frame may be a pack.PackedFrame (int16 codes, unpacked on the GPU); ingest (with data=None): "host" |
+        "packed" | "auto", as in encode_era5_as_bin.
         Returns one dict per frame: time_stamp, variables (channel names), the statistics of
         metrics.reconstruction_error (float64 [C] arrays in physical units; nonfinite int64 [C]), rmse_norm = rmse / std
         (the codec's per-channel normalisation std), bin_bytes (the container size, header included) and
@@ -882,6 +981,7 @@ class cra5_api:
         (bin_bytes + res_bytes); compression_ratio stays that of the .bin.  No budget applies here.  With save_root (and
         bins=None) the .res is written beside the .bin."""
         self.net._require_gpu()
+        self._ingest_arg(ingest)
         sel = self._select(coarsen=coarsen, regrid=regrid)
         k = sel.coarsen
         tol = self._residual_tol(max_error)
@@ -915,7 +1015,7 @@ class cra5_api:
             raise ValueError("evaluate_batch: time_stamps, data and bins must have the same length")
         paths = list(bins) if bins is not None else [None] * n
         reps = self._pipeline(workers).map(lambda it: self._evaluate_one(it[0], it[1], it[2], save_root, lat_weights, sel,
-                                                                         bool(spectrum), tol, quantiles),
+                                                                         bool(spectrum), tol, quantiles, ingest),
                                            list(zip(time_stamps, frames, paths)))
         for r in reps:
             r.update(extra)

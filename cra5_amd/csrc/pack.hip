@@ -12,6 +12,10 @@
 // Pack (pack_i16_kernel): one block per (channel, chunk).  The chunk's codes are cut where the DESTINATION is 8-byte
 // aligned: four codes per 8-byte store, their four floats one 16-byte load (of 4-byte alignment when source and destination
 // differ in phase); the up to three codes in front of and behind a plane's aligned part are written one by one.
+//
+// Unpack (unpack_i16_kernel; DESIGN.md section 4, "Packed int16 input"): the way in, cra5_unpack_i16_f32.  The same grid,
+// cut where the fp32 DESTINATION is 16-byte aligned: one 16-byte store per four values, their four codes one 8-byte load
+// (of 2-byte alignment when the phases differ), bytes swapped in registers when the codes come in the other byte order.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -204,6 +208,76 @@ __global__ __launch_bounds__(kThreads) void pack_i16_kernel(const float *__restr
   }
 }
 
+// "Packed int16 input": two float64 roundings (a multiply, then an add - never one fused operation, whatever the build's
+// contraction setting), one rounding to fp32, one fp32 multiply; the code FILL[c] gives the quiet NaN (a NaN FILL equals
+// no code)
+__device__ __forceinline__ float value_of_code(int q, double scale, double offset, double fill, float mul) {
+#pragma clang fp contract(off)
+  const double dq = (double)q;
+  const double p = dq * scale;
+  const double d = p + offset;
+  const float v = __double2float_rn(d) * mul;
+  return dq == fill ? __uint_as_float(0x7fc00000u) : v;
+}
+
+// the two codes of a 32-bit word, low half first; swapped: each half's bytes change places first
+__device__ __forceinline__ unsigned swap_halves(unsigned w, bool swapped) {
+  return swapped ? ((w & 0x00ff00ffu) << 8) | ((w >> 8) & 0x00ff00ffu) : w;
+}
+__device__ __forceinline__ int code_lo(unsigned w) { return (int)(short)(w & 0xffffu); }
+__device__ __forceinline__ int code_hi(unsigned w) { return (int)w >> 16; }
+
+struct __attribute__((aligned(2))) Word2A2 {   // four codes at 2-byte alignment: one 8-byte load
+  unsigned short h[4];
+};
+
+// q: [C][plane] int16 -> x: [C][plane].  xph: (address of x / 4) % 4 - value e is 16-byte aligned when (e + xph) % 4 == 0.
+__global__ __launch_bounds__(kThreads) void unpack_i16_kernel(const unsigned short *__restrict__ q, unsigned plane,
+                                                              int chunks, unsigned xph, const double *__restrict__ table,
+                                                              unsigned flags, float *__restrict__ x) {
+  const int c = blockIdx.x / chunks, b = blockIdx.x - c * chunks;
+  const int tid = threadIdx.x;
+  const bool swapped = (flags & CRA5_UNPACK_SWAPPED) != 0;
+  const double *t = table + (size_t)c * CRA5_UNPACK_FIELDS;
+  const double scale = t[0], offset = t[1], fill = t[2];
+  const float mul = (float)t[3];
+  const size_t g0 = (size_t)c * plane, g1 = g0 + plane;
+  const size_t a0 = min(((g0 + xph + 3) & ~(size_t)3) - xph, g1);
+  const size_t a1 = a0 < g1 ? ((g1 + xph) & ~(size_t)3) - xph : a0;
+  auto one = [&](size_t e) { x[e] = value_of_code(code_lo(swap_halves(q[e], swapped)), scale, offset, fill, mul); };
+  if (b == 0) {
+    // the plane's head [g0, a0) and tail [a1, g1): at most three values each
+    if (g0 + tid < a0) one(g0 + tid);
+    if (tid >= 64 && a1 + (tid - 64) < g1) one(a1 + (tid - 64));
+  }
+  const size_t n_groups = (a1 - a0) / 4;
+  const size_t j1 = min(n_groups, (size_t)(b + 1) * kChunkGroups);
+  auto group = [&](size_t e, const Word2A2 &v) {
+    const unsigned w0 = swap_halves(v.h[0] | ((unsigned)v.h[1] << 16), swapped);
+    const unsigned w1 = swap_halves(v.h[2] | ((unsigned)v.h[3] << 16), swapped);
+    float4 o;
+    o.x = value_of_code(code_lo(w0), scale, offset, fill, mul);
+    o.y = value_of_code(code_hi(w0), scale, offset, fill, mul);
+    o.z = value_of_code(code_lo(w1), scale, offset, fill, mul);
+    o.w = value_of_code(code_hi(w1), scale, offset, fill, mul);
+    *reinterpret_cast<float4 *>(x + e) = o;
+  };
+  size_t j = (size_t)b * kChunkGroups + tid;
+  // four loads in flight per thread
+  for (; j + 3 * kThreads < j1; j += 4 * kThreads) {
+    Word2A2 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const Word2A2 *>(q + a0 + 4 * (j + u * kThreads));
+#pragma unroll
+    for (int u = 0; u < 4; ++u) group(a0 + 4 * (j + u * kThreads), v[u]);
+  }
+#pragma unroll 1
+  for (; j < j1; j += kThreads) {
+    const Word2A2 v = *reinterpret_cast<const Word2A2 *>(q + a0 + 4 * j);
+    group(a0 + 4 * j, v);
+  }
+}
+
 bool dims_ok(int C, size_t plane) { return C > 0 && plane > 0 && plane <= 0x7fffffffu; }
 
 int bands_of(size_t plane) { return (int)((plane + kBandElems - 1) / kBandElems); }
@@ -241,6 +315,18 @@ int cra5_pack_i16_f32(const float *x, int C, size_t plane, const double *table, 
   const unsigned qph = (unsigned)(((uintptr_t)q / 2) % 4);
   hipLaunchKernelGGL(pack_i16_kernel, dim3(C * chunks), dim3(kThreads), 0, (hipStream_t)stream, x, (unsigned)plane, chunks,
                      qph, table, (unsigned short *)q);
+  return (int)hipGetLastError();
+}
+
+int cra5_unpack_i16_f32(const int16_t *q, int C, size_t plane, const double *table, unsigned flags, float *x,
+                        void *stream) {
+  if (!q || !table || !x || !dims_ok(C, plane)) return CRA5_ERR_ARG;
+  if ((uintptr_t)q % 2 || (uintptr_t)x % 4 || (uintptr_t)table % 8 || (flags & ~CRA5_UNPACK_SWAPPED)) return CRA5_ERR_ARG;
+  const int chunks = (int)((plane / 4 + kChunkGroups - 1) / kChunkGroups) + (plane < 4 ? 1 : 0);
+  if ((size_t)C * chunks > 0x7fffffffu) return CRA5_ERR_ARG;
+  const unsigned xph = (unsigned)(((uintptr_t)x / 4) % 4);
+  hipLaunchKernelGGL(unpack_i16_kernel, dim3(C * chunks), dim3(kThreads), 0, (hipStream_t)stream,
+                     (const unsigned short *)q, (unsigned)plane, chunks, xph, table, flags, x);
   return (int)hipGetLastError();
 }
 

@@ -858,6 +858,33 @@ def pack_i16(x, table, out=None):
     return out
 
 
+UNPACK_FIELDS = ("scale", "offset", "fill", "mul")   # CRA5_UNPACK_* order
+UNPACK_SWAPPED = 1                                   # CRA5_UNPACK_SWAPPED
+
+
+def unpack_i16(q, table, swapped=False, out=None):
+    """cra5_unpack_i16_f32: the fp32 values of the contiguous int16 device codes q [C, H, W] under `table` (fp64 device
+    [C, len(UNPACK_FIELDS)]: scale, offset, fill code (NaN: none), fp32-exact multiplier) -> fp32 device tensor shaped
+    like q (`out`): NaN for the fill code, else float(double(q) * scale + offset) * float(mul), the float64 multiply and
+    add rounded separately ("Packed int16 input").  swapped: the codes' bytes are in the other
+    order and are swapped in registers.  On the current stream."""
+    if not (isinstance(q, torch.Tensor) and q.is_cuda and q.dtype == torch.int16 and q.is_contiguous()):
+        raise TypeError("unpack_i16 takes a contiguous int16 device tensor [C, H, W]")
+    if q.dim() != 3 or q.numel() == 0 or q.shape[1] * q.shape[2] >= 1 << 31:
+        raise ValueError(f"unpack_i16: q {tuple(q.shape)} must be a non-empty [C, H, W] with H * W < 2^31")
+    C, plane = int(q.shape[0]), int(q.shape[1] * q.shape[2])
+    _pack_f64("unpack_i16", "table", table, (C, len(UNPACK_FIELDS)), q.device)
+    if out is None:
+        out = torch.empty(tuple(q.shape), device=q.device, dtype=torch.float32)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()):
+        raise TypeError(f"unpack_i16: out must be a contiguous fp32 device tensor {list(q.shape)}")
+    elif tuple(out.shape) != tuple(q.shape) or out.device != q.device:
+        raise ValueError(f"unpack_i16: out must be {list(q.shape)} on the codes' device, got {tuple(out.shape)} on {out.device}")
+    check(lib().cra5_unpack_i16_f32(_p(q), C, plane, _p(table), UNPACK_SWAPPED if swapped else 0, _p(out), _stream()),
+          "cra5_unpack_i16_f32")
+    return out
+
+
 SPECTRUM_MAX_W = 1440    # CRA5_SPECTRUM_MAX_W
 _TWIDDLES = {}           # (W, device) -> fp64 device [W, 2]: (cos, sin) of -2 pi j / W
 

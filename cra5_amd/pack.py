@@ -119,6 +119,215 @@ def error_bound(scale_factor, lo, hi):
     return np.asarray(scale_factor, dtype=np.float64) * (0.5 + 2.0 ** -30) + 2.0 ** -50 * np.maximum(np.abs(lo), np.abs(hi))
 
 
+# ---- packed int16 input ("Packed int16 input") -------------------------------------------------------
+
+_NATIVE = np.dtype(np.int16)
+_OTHER = _NATIVE.newbyteorder()
+
+
+class PackedFrame:
+    """One frame as int16 codes with their packing - what an encode entry point takes in place of a float32 host array:
+    the codes cross the host link (half the bytes) and are unpacked on the GPU (ops.unpack_i16).
+      q: one int16 array [C, H, W], or a sequence of C-contiguous int16 blocks [k_i, H, W] whose k_i sum to C (views
+        into file mappings: nothing is concatenated).  Native or swapped byte order, the same in every block.
+      scale_factor, add_offset: float64 [C], finite.  fill_value: a scalar, [C] (a NaN entry: no fill code for that
+        channel) or None (no fill code at all).  multiplier: [C] of values exact in fp32 (tp: 1000), None: all ones.
+    x = float32(float64(q) * scale_factor + add_offset) * float32(multiplier), NaN at the fill code (unpack_f32).
+    ValueError for wrong shapes and dtypes, mixed byte orders and non-finite scale / offset / multiplier."""
+
+    def __init__(self, q, scale_factor, add_offset, fill_value=FILL, multiplier=None, files=()):
+        blocks = [q] if isinstance(q, np.ndarray) else list(q)
+        if not blocks or not all(isinstance(b, np.ndarray) for b in blocks):
+            raise ValueError("PackedFrame: q must be an int16 numpy array [C, H, W] or a sequence of int16 blocks [k, H, W]")
+        for b in blocks:
+            if b.dtype not in (_NATIVE, _OTHER) or b.ndim != 3 or b.size == 0:
+                raise ValueError(f"PackedFrame: every block must be a non-empty int16 array [k, H, W], got {b.dtype} {b.shape}")
+            if b.shape[1:] != blocks[0].shape[1:]:
+                raise ValueError(f"PackedFrame: the blocks differ in grid: {b.shape[1:]} and {blocks[0].shape[1:]}")
+            if b.dtype.isnative != blocks[0].dtype.isnative:
+                raise ValueError("PackedFrame: the blocks mix byte orders")
+        if isinstance(q, np.ndarray):
+            blocks = [np.ascontiguousarray(q)]
+        elif not all(b.flags["C_CONTIGUOUS"] for b in blocks):
+            raise ValueError("PackedFrame: every block must be C-contiguous")
+        C = sum(b.shape[0] for b in blocks)
+        self.blocks = blocks
+        self.shape = (C,) + tuple(blocks[0].shape[1:])
+        self.swapped = not blocks[0].dtype.isnative
+        self.transient = False      # cra5_api sets it on the frames it reads itself: closed once staged
+        self._files = list(files)
+
+        def per_channel(name, v, dtype=np.float64):
+            try:
+                a = np.array(v, dtype=dtype)
+            except (TypeError, ValueError):
+                raise ValueError(f"PackedFrame: {name} must be numbers, [{C}]") from None
+            if a.shape != (C,):
+                raise ValueError(f"PackedFrame: {name} must be [{C}], got {a.shape}")
+            return a
+        self.scale_factor = per_channel("scale_factor", scale_factor)
+        self.add_offset = per_channel("add_offset", add_offset)
+        if not (np.isfinite(self.scale_factor).all() and np.isfinite(self.add_offset).all()):
+            raise ValueError("PackedFrame: scale_factor and add_offset must be finite")
+        if fill_value is None:
+            fill_value = np.nan
+        if np.ndim(fill_value) == 0:
+            fill_value = np.full(C, fill_value, dtype=np.float64)
+        self.fill = per_channel("fill_value", fill_value)
+        given = self.fill[~np.isnan(self.fill)]
+        if not ((given == np.rint(given)).all() and (given >= -32768).all() and (given <= QMAX).all()):
+            raise ValueError("PackedFrame: a fill_value must be an int16 code (or NaN: none)")
+        self.multiplier = per_channel("multiplier", np.ones(C) if multiplier is None else multiplier)
+        with np.errstate(over="ignore"):
+            exact = self.multiplier.astype(np.float32).astype(np.float64) == self.multiplier
+        if not (np.isfinite(self.multiplier).all() and exact.all()):
+            raise ValueError("PackedFrame: every multiplier must be finite and exact in float32")
+
+    @classmethod
+    def from_decode(cls, d):
+        """The dict of decode_from_bin / decode_batch(pack=..., to_host=True) (codes under "x_hat" or "q") -> its frame:
+        a packed decode can be re-encoded directly."""
+        q = d["q"] if "q" in d else d["x_hat"]
+        if hasattr(q, "detach"):
+            q = q.detach().cpu().numpy()
+        q = np.asarray(q)
+        return cls(q.reshape(q.shape[-3:]), d["scale_factor"], d["add_offset"], d.get("fill_value", FILL))
+
+    @property
+    def nbytes(self):
+        return 2 * self.shape[0] * self.shape[1] * self.shape[2]
+
+    def table(self):
+        """float64 [C, 4]: scale, offset, fill (NaN: none), multiplier - ops.UNPACK_FIELDS, the kernel's table."""
+        return np.ascontiguousarray(np.stack([self.scale_factor, self.add_offset, self.fill, self.multiplier], axis=1))
+
+    def byteswapped(self):
+        """The same frame with its codes in the other byte order (a copy)."""
+        other = _OTHER if not self.swapped else _NATIVE
+        return PackedFrame([b.astype(other) for b in self.blocks], self.scale_factor, self.add_offset, self.fill,
+                           self.multiplier)
+
+    def close(self):
+        """Drop the blocks and close the files they map (read_era5_nc_packed); the frame is unusable afterwards."""
+        self.blocks = None
+        files, self._files = self._files, []
+        for f in files:
+            f.close()
+
+
+def unpack_f32(frame):
+    """PackedFrame -> float32 numpy [C, H, W]: the definition of "Packed int16 input" on the host, channel by channel -
+    float64 multiply, float64 add, one rounding to float32, one float32 multiply; NaN at the fill code."""
+    out = np.empty(frame.shape, dtype=np.float32)
+    mul = frame.multiplier.astype(np.float32)
+    c = 0
+    for blk in frame.blocks:
+        for k in range(blk.shape[0]):
+            q = blk[k].astype(np.int16)                       # (the values, in native order)
+            d = q.astype(np.float64) * frame.scale_factor[c]
+            d += frame.add_offset[c]
+            with np.errstate(over="ignore", invalid="ignore"):
+                x = d.astype(np.float32) * mul[c]
+            if not np.isnan(frame.fill[c]):
+                x[q == np.int16(frame.fill[c])] = np.float32(np.nan)
+            out[c] = x
+            c += 1
+    return out
+
+
+def read_era5_nc_packed(local_root, time_stamp, vnames, pressure_level, reason=None):
+    """The frame of {local_root}/ERA5/{yyyy}/{ts}_pressure.nc / {ts}_single.nc as a PackedFrame whose blocks are views
+    of the file mappings, in channel order (pressure variables x `pressure_level`, then the single-level variables; the
+    file's level axis may hold more levels, in any order) - or None when the files do not hold plain packed int16:
+    a file that is not NetCDF-3, a needed variable that is not i2, lacks scale_factor / add_offset or has a _FillValue
+    and a missing_value that differ (the caller then reads the frame through read_data_from_nc).  tp gets the multiplier
+    1000 (the model works in tp x 1000).  reason: a list that receives "<file>: <why>" with a None.  The mappings stay
+    open until close() of the frame."""
+    opened = []
+    frame = _read_packed(f"{local_root}/ERA5/{time_stamp[:4]}", time_stamp, vnames, pressure_level, opened, reason)
+    if frame is None:
+        for f in opened:        # (no view of their mappings is alive any more)
+            f.close()
+    return frame
+
+
+def _read_packed(folder, time_stamp, vnames, pressure_level, opened, reason):
+    from scipy.io import netcdf_file
+
+    def give_up(path, why):
+        if reason is not None:
+            reason.append(f"{path}: {why}")
+
+    def open_nc(path):
+        with open(path, "rb") as f:
+            magic = f.read(4)
+        if magic[:3] != b"CDF":
+            return None
+        opened.append(netcdf_file(path, "r", mmap=True, maskandscale=False))
+        return opened[-1]
+
+    blocks, scale, offset, fill, mul = [], [], [], [], []
+
+    def take(path, var, name, rows):
+        """`rows` (lists of consecutive indices) of the variable's [n, H, W] codes -> blocks; False: not plain packed i2."""
+        att = var._attributes
+        if var.data.dtype not in (_NATIVE, _OTHER):
+            return give_up(path, f"variable {name!r} is {var.data.dtype.name}, not int16")
+        if "scale_factor" not in att or "add_offset" not in att:
+            return give_up(path, f"variable {name!r} has no scale_factor / add_offset")
+        fv = [np.asarray(att[k]).reshape(-1)[0] for k in ("_FillValue", "missing_value") if k in att]
+        if len(fv) == 2 and fv[0] != fv[1]:
+            return give_up(path, f"variable {name!r} has _FillValue {fv[0]} and missing_value {fv[1]}")
+        n = 0
+        for run in rows:
+            blk = var.data[0][run[0]:run[-1] + 1] if var.data.ndim == 4 else var.data[0][None]
+            if not blk.flags["C_CONTIGUOUS"]:
+                return give_up(path, f"variable {name!r} is not stored contiguously")
+            blocks.append(blk)
+            n += blk.shape[0]
+        scale.extend([float(np.asarray(att["scale_factor"]).reshape(-1)[0])] * n)
+        offset.extend([float(np.asarray(att["add_offset"]).reshape(-1)[0])] * n)
+        fill.extend([float(fv[0]) if fv else np.nan] * n)
+        mul.extend([1000.0 if name == "tp" else 1.0] * n)
+        return True
+
+    if vnames["pressure"]:
+        path = f"{folder}/{time_stamp}_pressure.nc"
+        nc = open_nc(path)
+        if nc is None:
+            return give_up(path, "not a NetCDF-3 file")
+        pha = [float(v) for v in nc.variables["level"][:]]
+        if not all(v in pha for v in pressure_level):
+            return give_up(path, "a level of the model is missing from the level axis")
+        level_mapping = [pha.index(v) for v in pressure_level]
+        runs = [[level_mapping[0]]]
+        for lv in level_mapping[1:]:
+            if lv == runs[-1][-1] + 1:
+                runs[-1].append(lv)
+            else:
+                runs.append([lv])
+        for name in vnames["pressure"]:
+            var = nc.variables[name]
+            if var.data.ndim != 4:
+                return give_up(path, f"variable {name!r} is not (time, level, latitude, longitude)")
+            if not take(path, var, name, runs):
+                return None
+    if vnames["single"]:
+        path = f"{folder}/{time_stamp}_single.nc"
+        nc = open_nc(path)
+        if nc is None:
+            return give_up(path, "not a NetCDF-3 file")
+        for name in vnames["single"]:
+            var = nc.variables[name]
+            if var.data.ndim != 3:
+                return give_up(path, f"variable {name!r} is not (time, latitude, longitude)")
+            if not take(path, var, name, [[0]]):
+                return None
+    if any(b.shape[1:] != blocks[0].shape[1:] for b in blocks):
+        return give_up(folder, "the variables differ in grid")
+    return PackedFrame(blocks, scale, offset, fill, mul, files=opened)
+
+
 # ---- NetCDF ------------------------------------------------------------------------------------------------------------
 
 _EPOCH = datetime.datetime(1900, 1, 1)

@@ -431,6 +431,21 @@ int cra5_pack_range_f32(const float *x, int C, size_t plane, const double *fixed
                         double *out, void *stream);
 int cra5_pack_i16_f32(const float *x, int C, size_t plane, const double *table, int16_t *q, void *stream);
 
+/* Packed int16 input (csrc/pack.hip; DESIGN.md section 4, "Packed int16 input"): the inverse direction, for frames that
+ * arrive as int16 codes with scale_factor / add_offset / _FillValue (the NetCDF layout of ERA5).  q [C][plane] int16
+ * (2-byte aligned), x [C][plane] fp32 (4-byte aligned), table device fp64 [C][CRA5_UNPACK_FIELDS] = (SCALE, OFFSET, FILL,
+ * MUL); MUL holds a value that is exact in fp32.  Per channel c and code q:
+ *   q == FILL[c] (FILL[c] not NaN: a NaN FILL is "no fill code")  ->  x = the quiet NaN 0x7fc00000; otherwise
+ *   d = (double)q * SCALE[c], rounded to float64;  d = d + OFFSET[c], rounded to float64 (two roundings, never a fused
+ *   multiply-add);  x = (float)d, to nearest even;  x = x * (float)MUL[c], one fp32 multiply.
+ * flags: CRA5_UNPACK_SWAPPED - the two bytes of every code are in the other order (NetCDF-3 stores big-endian) and are
+ * swapped in registers.  One launch on `stream`; nothing outside x is written, q and table are only read.  Any NULL or
+ * misaligned pointer, C <= 0, plane == 0 or >= 2^31 and any unknown flag bit return CRA5_ERR_ARG before any device work. */
+#define CRA5_UNPACK_FIELDS 4
+#define CRA5_UNPACK_SWAPPED 1u
+int cra5_unpack_i16_f32(const int16_t *q, int C, size_t plane, const double *table, unsigned flags, float *x,
+                        void *stream);
+
 /* Zonal power spectra of a frame pair (csrc/spectrum.hip): x_hat, x [C][H][W] fp32, d = x_hat - x in
  * fp32.  For a row f(c, h, .):  F(c, h, k) = sum_w f(c, h, w) e^(-2 pi i k w / W),  k = 0 .. K - 1,  K = W / 2 + 1, and
  *   P_f(c, k) = (1 / H) sum_h L(h) m_k |F(c, h, k)|^2 / W^2,   m_k = 1 for k = 0 and for k = W / 2 of an even W, else 2,
