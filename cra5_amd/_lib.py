@@ -70,6 +70,11 @@ SIGNATURES = {
     "cra5_gather_token_lattice": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t] + [c_int] * 8 + [c_void_p]),
     "cra5_strided_scatter_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                          c_void_p, c_int, c_int, c_int, c_void_p]),
+    "cra5_gather_token_list": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_void_p, c_int, c_void_p]),
+    "cra5_points_from_cols": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cra5_points_from_image": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_void_p, c_void_p]),
     "cra5_coarsen_f32": (c_int, [c_void_p] + [c_int] * 14 + [c_void_p] * 3 + [c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "cra5_regrid_f32": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 3 + [c_int] + [c_void_p] * 4 + [c_int, c_void_p] +
                         [c_int] * 3 + [c_void_p, c_int, c_void_p, c_void_p]),

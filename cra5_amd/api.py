@@ -95,20 +95,29 @@ class Selection(NamedTuple):
     shape: tuple                    # (C', Hb, Wb) of one decoded frame
     whole: bool                     # no argument asked for a subset: decode_from_bin's dict carries no extra keys
     regrid: Optional[dict] = None   # the target grid's plan (VAEformer._regrid_arg); lat / lon / the bounds are then its
+    points: Optional[dict] = None   # the point list's plan (VAEformer._points_arg); shape is then (C', P), lat / lon [P]
 
     @property
     def model(self):
-        """The keyword arguments of _decompress_frame / _decode_guarded / decode_latent (regrid only when asked for)."""
+        """The keyword arguments of _decompress_frame / _decode_guarded / decode_latent (regrid / points only when asked
+        for)."""
         kw = dict(channels=self.channels, box=self.box, step=self.step, coarsen=self.coarsen)
         if self.regrid is not None:
             kw["regrid"] = self.regrid
+        if self.points is not None:
+            kw["points"] = self.points
         return kw
 
     @property
     def meta(self):
         """The result dicts' keys: variables, lat, lon - with coarsen also coarsen, lat_bnds, lon_bnds; with regrid also
-        regrid (the method), lat_bnds, lon_bnds."""
+        regrid (the method), lat_bnds, lon_bnds; with points: lat, lon are the points' (float64 [P]), also points (the
+        method) and, for "nearest", node_lat, node_lon - the grid point each one took."""
         meta = dict(variables=self.names, lat=self.lat, lon=self.lon)
+        if self.points is not None:
+            meta.update(points=self.points["method"])
+            if self.points["method"] == "nearest":
+                meta.update(node_lat=self.points["node_lat"], node_lon=self.points["node_lon"])
         if self.coarsen is not None:
             meta.update(coarsen=self.coarsen, lat_bnds=self.lat_bnds, lon_bnds=self.lon_bnds)
         if self.regrid is not None:
@@ -348,14 +357,24 @@ class cra5_api:
         """The names of the channels `chans`, in that order; None: of every channel of the model."""
         return [self.channels_to_vname.get(c, str(c)) for c in (chans if chans is not None else range(self.net.cfg['out_chans']))]
 
-    def _select(self, variables=None, region=None, stride=None, coarsen=None, regrid=None):
+    def _select(self, variables=None, region=None, stride=None, coarsen=None, regrid=None, points=None):
         """The arguments of the decode methods -> their Selection; without any of them the whole grid's.  regrid (a
         regrid.Grid or its plan): the frame on that target grid - not together with region / stride / coarsen, the
-        target grid is the region and the resolution."""
+        target grid is the region and the resolution.  points (a points.Points, a [P, 2] array of (lat, lon) or its
+        plan): the frame at those positions, [C', P] - with variables only."""
         H, W = self.net.cfg['img_size']
         step, k = subset._stride_or_coarsen(stride, coarsen, H, W)
-        whole = variables is None and region is None and step is None and k is None and regrid is None
+        whole = variables is None and region is None and step is None and k is None and regrid is None and points is None
         chans = subset.resolve_variables(variables, self.vname_to_channels)
+        if points is not None:
+            for name, v in (("region", region), ("stride", step), ("coarsen", k), ("regrid", regrid)):
+                if v is not None:
+                    raise ValueError(f"points and {name}: pass one of the two - a point list names its own positions")
+            names = self._names(chans)
+            channels = self.net._selection_args(chans)[0]
+            plan = self.net._points_arg(points)
+            return Selection(channels, None, None, None, names, plan["lat"], plan["lon"], None, None,
+                             (len(names), plan["P"]), False, None, plan)
         if regrid is not None:
             for name, v in (("region", region), ("stride", step), ("coarsen", k)):
                 if v is not None:
@@ -674,7 +693,7 @@ class cra5_api:
             self._log(phase, t_d)
         if side is not None:
             self._residual_correct(x_hat, side, sel, what)
-        return x_hat.reshape(x_hat.shape[-3:])
+        return x_hat.reshape(x_hat.shape[-len(sel.shape):])
 
     def _decode_one(self, i, path, denorm, sel, out=None, sink=None, res_path=None, pack=None):
         """One frame of the batch decode on the calling frame thread: .bin -> the Selection `sel` of x_hat -> this thread's
@@ -766,10 +785,10 @@ class cra5_api:
         an assert that `python -O` drops - ADVICE r5)."""
         if out is None:
             return
-        C, H, W = frame_shape
-        if not isinstance(out, np.ndarray) or out.dtype != dtype or tuple(out.shape) != (n, C, H, W) \
+        want = (n,) + tuple(frame_shape)          # ([n, C', P] with points=)
+        if not isinstance(out, np.ndarray) or out.dtype != dtype or tuple(out.shape) != want \
                 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
-            raise ValueError(f"`out` must be a writeable C-contiguous {np.dtype(dtype).name} numpy array of shape [{n}, {C}, {H}, {W}]"
+            raise ValueError(f"`out` must be a writeable C-contiguous {np.dtype(dtype).name} numpy array of shape {list(want)}"
                              f" (got {type(out).__name__} {getattr(out, 'dtype', None)} {getattr(out, 'shape', None)})")
 
     def roundtrip_batch(self, time_stamps, data=None, save_root=None, workers=12, sink=None, out=None,
@@ -794,7 +813,8 @@ class cra5_api:
         return self._pipeline(workers).map(one, [(i, ts, a) for i, (ts, a) in enumerate(zip(time_stamps, frames))])
 
     def decode_batch(self, time_stamps=None, paths=None, return_format='de_normalized', out=None, workers=12, sink=None,
-                     variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None, regrid=None):
+                     variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None, regrid=None,
+                     points=None):
         """decode_from_bin for many frames.  Returns a list of HOST float32 arrays [C, H, W] (views of `out`
         [n, C, H, W] when given, fresh arrays otherwise); the D2H of each reconstruction goes through the
         decoding thread's pinned buffer and overlaps the other frames' work.  `sink(i, frame)`: called on the decoding
@@ -809,6 +829,9 @@ class cra5_api:
         and the cells' lat_bnds / lon_bnds.
         regrid (decode_from_bin): a regrid.Grid - every frame is [C', Ho, Wo] on that target grid, regridded on the device;
         only the target grid crosses the host link.  `out`, `sink` and `pack` work on the regridded frame.
+        points (decode_from_bin): a points.Points or a [P, 2] array of (lat, lon), with variables only - every frame is
+        [C', P], the decode at those positions; `out` must be [n, C', P], `sink` gets [C', P] views.  series_batch keeps
+        the frames on the device and returns one [T, C', P] array.
         residual (decode_from_bin): True - the .res beside every .bin -, or one sidecar path per frame; every frame is
         corrected on the device before it crosses the host link.
         pack (decode_from_bin; only with return_format 'de_normalized'): "int16" / True / {variable: (lo, hi)} - every frame
@@ -818,15 +841,29 @@ class cra5_api:
         scale_factor, add_offset, vmin, vmax, nonfinite, saturated, fill_value; `out` must be a C-contiguous int16 array
         [n, C', Hb, Wb] and q is its view; `sink(i, item)` receives the dict, q a view of the pinned buffer."""
         return self._decode_batch(time_stamps, paths, return_format, out, workers, sink, variables, region, stride, coarsen,
-                                  residual, pack, regrid=regrid)
+                                  residual, pack, regrid=regrid, points=points)
+
+    @staticmethod
+    def _points_alone(what, points, residual=None, pack=None, return_format=None):
+        """points= of `what` goes with variables= only: ValueError together with residual, pack or the latent."""
+        if points is None:
+            return
+        for name, v in (("residual", residual), ("pack", pack)):
+            if v is not None and v is not False:
+                raise ValueError(f"{what}: points= with {name}= is not supported - {name} works on grid frames, a point "
+                                 f"list returns [C', P]")
+        if return_format == 'latent':
+            raise ValueError(f"{what}: return_format='latent' returns the latent; points select positions of the "
+                             "reconstruction")
 
     def _decode_batch(self, time_stamps, paths, return_format, out, workers, sink, variables, region, stride, coarsen,
-                      residual, pack, what="decode_batch", per_variable=False, regrid=None):
+                      residual, pack, what="decode_batch", per_variable=False, regrid=None, points=None):
         if paths is None:
             paths = [self._bin_path(ts) for ts in time_stamps]
+        self._points_alone(what, points, residual, pack, return_format)
         denorm = self._denorm_arg(return_format)
         self.net._require_gpu()
-        sel = self._select(variables, region, stride, coarsen, regrid)
+        sel = self._select(variables, region, stride, coarsen, regrid, points)
         sides = self._residual_arg(what, residual, list(paths), return_format, sel.coarsen, sel.regrid)
         pk = self._pack_arg(what, pack, return_format, sel, per_variable)
         self._check_out(out, len(paths), sel.shape, np.int16 if pk is not None else np.float32)
@@ -1124,6 +1161,61 @@ class cra5_api:
         self._log("d2h", t0)
         return res
 
+    def series_batch(self, time_stamps=None, paths=None, points=None, variables=None, return_format='de_normalized',
+                     workers=12, to_host=True):
+        """Time series at stations or along a track: every .bin is decoded through the frame pipeline exactly as
+        decode_batch(points=) decodes it, and frame i's un-embed writes its [C', P] values straight into series[i] on the
+        device - nothing crosses the host link per frame.  The finished array comes back once.
+          points: a cra5_amd.points.Points or a [P, 2] array of (lat, lon) (decode_from_bin); variables: names, or None
+          for every channel; return_format: 'de_normalized' | 'normalized'.
+        Returns dict(series: float32 [T, C', P] - a HOST array, or with to_host=False a device tensor -, time_stamps (or
+        paths, whichever was given), variables, lat, lon (the points', float64 [P]), points (the method) and, for
+        "nearest", node_lat / node_lon).  series[i] is decode_from_bin(..., points=, variables=)'s x_hat of frame i bit
+        for bit; every frame owns its slot, so the result does not depend on `workers`.  A frame that fails (a missing
+        file, a StreamDesyncError) ends the call with that frame's error."""
+        if points is None:
+            raise ValueError("series_batch needs points= (a cra5_amd.points.Points or a [P, 2] array of (lat, lon))")
+        given = "paths" if paths is not None else "time_stamps"
+        if paths is None:
+            if time_stamps is None:
+                raise ValueError("series_batch needs time_stamps or paths")
+            time_stamps = list(time_stamps)
+            paths = [self._bin_path(ts) for ts in time_stamps]
+        paths = list(paths)
+        if not paths:
+            raise ValueError("series_batch: no frame given")
+        self._points_alone("series_batch", points, return_format=return_format)
+        denorm = self._denorm_arg(return_format)
+        sel = self._select(variables, points=points)
+        self.net._require_gpu()
+        T = len(paths)
+        series = torch.empty((T,) + sel.shape, device=self.net.device, dtype=torch.float32)
+        torch.cuda.current_stream().synchronize()
+
+        def one(i):
+            strings, shape, _ = self._read_frame(paths[i])
+            with torch.no_grad():
+                t_d = time.perf_counter()
+                self.net._decompress_frame(strings[0][0], strings[1][0], shape, True,
+                                           mean=self._mean_flat if denorm else None,
+                                           std=self._std_flat if denorm else None, out=series[i], **sel.model)
+                self._log("decompress", t_d)
+        self._pipeline(workers).map(one, list(range(T)))
+
+        res = dict(series=series, **{given: paths if given == "paths" else time_stamps}, **sel.meta)
+        if not to_host:
+            return res
+        t0 = time.perf_counter()
+        host = np.empty(tuple(series.shape), dtype=np.float32)
+        per = max(1, min(T, ops.COPY_CHUNK // max(1, 4 * sel.shape[0] * sel.shape[1])))     # frames per staged copy
+        pin = self.net._pinned("api_series_out", (per,) + sel.shape, torch.float32)
+        for i in range(0, T, per):
+            n = min(per, T - i)
+            ops.copy_d2h_staged(host[i:i + n], series[i:i + n], pin, threads=self.runtime.copy_threads)
+        self._log("d2h", t0)
+        res["series"] = host
+        return res
+
     # ------------------------------------------------------------------ residual layer (cra5_amd/residual.py)
     def _residual_tol(self, max_error):
         """max_error -> the per-channel tolerance, float32 numpy [C] in physical units (residual.resolve_tolerance), or
@@ -1281,14 +1373,16 @@ class cra5_api:
         with torch.no_grad():
             return self.net.decompress(lstrings, shape, return_format='latent')
 
-    def latent_to_reconstruction(self, y_hat, variables=None, region=None, stride=None, coarsen=None, regrid=None):
-        """cra5_api.py:146-151 (normalised units).  variables / region / stride / coarsen / regrid: that subset, or that
-        target grid (decode_from_bin)."""
+    def latent_to_reconstruction(self, y_hat, variables=None, region=None, stride=None, coarsen=None, regrid=None,
+                                 points=None):
+        """cra5_api.py:146-151 (normalised units).  variables / region / stride / coarsen / regrid / points: that subset,
+        that target grid or those positions ([B, C', P]) (decode_from_bin)."""
         with torch.no_grad():
-            return self.net.decode_latent(y_hat, **self._select(variables, region, stride, coarsen, regrid).model)
+            return self.net.decode_latent(y_hat, **self._select(variables, region, stride, coarsen, regrid, points).model)
 
     def decode_from_bin(self, time_stamp=None, custom_path=None, return_format='de_normalized', to_host=False, out=None,
-                        variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None, regrid=None):
+                        variables=None, region=None, stride=None, coarsen=None, residual=None, pack=None, regrid=None,
+                        points=None):
         """cra5_api.py:153-192.  `to_host=True` (or `out=` a float32 array of the frame's shape): `x_hat` comes back
         as a HOST numpy array through the pinned staging buffer instead of a device tensor.
         variables: names of channel_vname_mapping() (e.g. ["z_500", "t_850", "t2m"]), output channels in that order;
@@ -1313,6 +1407,14 @@ class cra5_api:
         crosses the host link.  The un-embed runs on the source box the target needs.  Not together with region / stride
         / coarsen (the target grid is the region), residual or return_format 'latent' (ValueError).  The dict also carries
         `regrid` (the method), `lat`, `lon`, `lat_bnds` [Ho, 2] (north, south) and `lon_bnds` [Wo, 2] (west, east).
+        points: a cra5_amd.points.Points(lat, lon, method="bilinear" | "nearest"), or a plain [P, 2] array of (lat, lon)
+        rows (bilinear) - stations, a track; any order, duplicates allowed: x_hat is [C', P], the full decode at those
+        positions in the order given.  "nearest" is the grid point's value bit for bit (the dict carries node_lat /
+        node_lon, the point taken), "bilinear" the bits of regrid=Grid([lat], [lon]) at that point (DESIGN.md section 4,
+        "Point sampling").  Only the tokens whose patches hold a node are un-embedded, and only P values per variable
+        cross the link.  With variables= only: ValueError together with region / stride / coarsen / regrid / residual /
+        pack / return_format 'latent'.  The dict also carries `variables`, `lat`, `lon` (the points', float64 [P], lon in
+        [0, 360)) and `points` (the method).
         residual: None | True (the .res beside the .bin: the same path with the extension replaced; a missing file is an
         error) | a sidecar path, written by encode_era5_as_bin(max_error=...).  Its corrections are added on the GPU, in
         place on the decode's output before it goes anywhere else: every point of the corrected channels is then the truth
@@ -1330,13 +1432,14 @@ class cra5_api:
         scale_factor + add_offset is within scale_factor * (0.5 + 2^-30) + 2^-50 max(|lo|, |hi|) of the decoded value; with
         residual=True the frame is corrected first and then packed, and the distance to the truth is bounded by the
         sidecar's tolerance plus that packing bound.  Only with return_format 'de_normalized' (ValueError otherwise)."""
+        self._points_alone("decode_from_bin", points, residual, pack, return_format)
         if return_format == 'latent' and (variables is not None or region is not None or stride is not None
                                           or coarsen is not None or regrid is not None):
             raise ValueError("decode_from_bin: return_format='latent' returns the latent; variables / region / stride / "
                              "coarsen / regrid select a subset of the reconstruction")
         if return_format != 'latent':
             self._denorm_arg(return_format)
-        sel = self._select(variables, region, stride, coarsen, regrid)
+        sel = self._select(variables, region, stride, coarsen, regrid, points)
         bin_path = custom_path or self._bin_path(time_stamp)
         res_path = self._residual_arg("decode_from_bin", residual if residual is None or isinstance(residual, bool) else [residual],
                                       [bin_path], return_format, sel.coarsen, sel.regrid)[0]
@@ -1355,12 +1458,14 @@ class cra5_api:
                 x_hat = self.net._decode_guarded(y_hat[0], mean=self._mean_flat, std=self._std_flat, **sel.model)
                 if side is not None:
                     self._residual_correct(x_hat, side, sel, res_path)
+            if sel.points is not None:
+                x_hat = x_hat.reshape(sel.shape)         # [C', P] from either format
             ht, dt = (np.float32, torch.float32) if pk is None else (np.int16, torch.int16)
             if pk is not None:
                 x_hat, table, fixed = self._pack_device(x_hat.reshape(x_hat.shape[-3:]), pk)
                 stats = _pk.frame_stats(table.cpu().numpy(), fixed)
             if to_host or out is not None:
-                src = x_hat.reshape(x_hat.shape[-3:]).contiguous()
+                src = x_hat.reshape(x_hat.shape[-len(sel.shape):]).contiguous()
                 if out is None:
                     out = np.empty(tuple(src.shape), dtype=ht)
                 if out.dtype != ht or tuple(out.shape) != tuple(src.shape) or not out.flags["C_CONTIGUOUS"]:

@@ -24,7 +24,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcra5_amd.so")
 SOURCES = ["host_entropy.cpp", "gemm_f32.hip", "gemm_split_f16.hip", "attention_f32.hip", "attention_split_f16.hip",
-           "elementwise.hip", "hyper.hip", "metrics.hip", "pack.hip", "quantile.hip", "residual.hip", "runtime.hip", "spectrum.hip",
+           "elementwise.hip", "hyper.hip", "metrics.hip", "pack.hip", "points.hip", "quantile.hip", "residual.hip", "runtime.hip", "spectrum.hip",
            "subset.hip", "timestats.hip", "window_reduce.hip"]
 SOURCES = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
 HEADERS = [os.path.join(ROOT, "include", "cra5_amd.h"), os.path.join(CSRC, "split.h"), os.path.join(CSRC, "rans_resolve.h"),

@@ -633,6 +633,103 @@ def strided_scatter(g, rows, cols, cls, n_cc, C, mean=None, std=None, out=None):
     return out
 
 
+def gather_token_list(src, out, tok):
+    """cra5_gather_token_list: rows tok[r] of the token-major matrix `src` -> rows r of `out`, verbatim.  src / out: both
+    SplitMat (split or plain rows; `out` takes src's layout) or both 2-D fp32 device tensors with unit inner stride; tok:
+    a contiguous int32 device vector.  A tok[r] outside src's rows reads nothing: row r is all 0xFF bytes (NaN)."""
+    if not (isinstance(tok, torch.Tensor) and tok.is_cuda and tok.dtype == torch.int32 and tok.dim() == 1
+            and tok.is_contiguous() and tok.numel() > 0):
+        raise ValueError("gather_token_list: tok must be a contiguous non-empty int32 device vector")
+    n = tok.numel()
+    if isinstance(src, SplitMat):
+        if not isinstance(out, SplitMat) or out.Kp != src.Kp or out.K != src.K or out.rows != n:
+            raise ValueError("gather_token_list: `out` must be a SplitMat of len(tok) rows and src's K")
+        _dev(src.data, out.data)
+        row_bytes = 2 * src.Kp if src.plain else 4 * src.Kp       # a plain row holds Kp halves, a split row 2 * Kp
+        s_t, d_t, n_src = src.data, out.data, src.rows
+        out.scale_inv, out.plain = src.scale_inv, src.plain
+    else:
+        _dev(src, out)
+        if out.dim() != 2 or src.dim() != 2 or out.shape[1] != src.shape[1] or out.shape[0] != n or src.dtype != out.dtype:
+            raise ValueError("gather_token_list: `out` must be [len(tok), K] of src's K and dtype")
+        row_bytes = src.shape[1] * src.element_size()
+        s_t, d_t, n_src = src, out, src.shape[0]
+    if s_t.device != tok.device or d_t.device != tok.device or s_t.shape[0] < n_src:
+        raise ValueError("gather_token_list: src, out and tok must lie on one device")
+    es = s_t.element_size()
+    check(lib().cra5_gather_token_list(_p(s_t), _row_stride(s_t) * es, _p(d_t), _row_stride(d_t) * es, row_bytes, n_src,
+                                       _p(tok), n, _stream()), "cra5_gather_token_list")
+    return out
+
+
+_POINT_TABLES = (("rows", torch.int32), ("cols", torch.int32), ("rw", torch.float64), ("cw", torch.float64))
+_POINT_PLAN_TABLES = _POINT_TABLES + (("pnode", torch.int32), ("tokens", torch.int32), ("contrib", torch.int32))
+
+
+def points_tables(plan, device):
+    """The device tables of ops.points_from_image (points.Points.taps: rows / cols int32 [P, 2], rw / cw fp64 [P, 2]) and,
+    for a Points.plan, of ops.gather_token_list / ops.points_from_cols as well (pnode int32 [P, 4], tokens int32 [M],
+    contrib int32 [n_nodes, 4]): the plan's geometry plus those copies."""
+    return _device_tables(plan, plan, _POINT_PLAN_TABLES if "contrib" in plan else _POINT_TABLES, device)
+
+
+def _points_args(what, t, spec, src, out, C):
+    _dev(src, out)
+    ok = isinstance(t, dict) and all(isinstance(t.get(k), torch.Tensor) and t[k].is_cuda and t[k].is_contiguous()
+                                     and t[k].dtype == dt and t[k].device == src.device for k, dt in spec)
+    if not ok:
+        raise ValueError(f"{what}: tables must come from ops.points_tables (contiguous int32 / fp64 tensors on the source's "
+                         "device)")
+    P = int(t["P"])
+    shapes = dict(rows=(P, 2), cols=(P, 2), rw=(P, 2), cw=(P, 2), pnode=(P, 4))
+    if any(k in shapes and tuple(t[k].shape) != shapes[k] for k, _ in spec):
+        raise ValueError(f"{what}: the tables do not belong to a plan of {P} points")
+    if out is None:
+        out = torch.empty((C, P), device=src.device, dtype=torch.float32)
+    if not (out.dtype == torch.float32 and out.is_contiguous() and out.numel() == C * P and out.shape[0] == C
+            and out.shape[-1] == P and out.device == src.device):
+        raise ValueError(f"{what}: out must be a contiguous fp32 [{C}, {P}] tensor on the source's device")
+    return P, out
+
+
+def points_from_cols(cols, tables, C, mean=None, std=None, out=None):
+    """cra5_points_from_cols: the plan's P points out of the column matrix cols (fp32 [M, >= C * kh * kw], unit inner
+    stride: the two-call un-embed of the plan's tokens, in their order, for C channels) -> fp32 [C, P].  tables:
+    points_tables(Points.plan(...), device).  mean / std [C]: de-normalised per node (x * std[c] + mean[c]) before the
+    interpolation."""
+    _dev(mean, std)
+    spec = tuple(s for s in _POINT_PLAN_TABLES if s[0] not in ("rows", "cols", "tokens"))
+    P, out = _points_args("points_from_cols", tables, spec, cols, out, C)
+    t = tables
+    kh, kw = t["patch"][:2]
+    M = int(t["tokens"].numel()) if isinstance(t.get("tokens"), torch.Tensor) else -1
+    if cols.dtype != torch.float32 or cols.dim() != 2 or cols.shape[0] != M or cols.shape[1] < C * kh * kw \
+            or t["contrib"].dim() != 2 or t["contrib"].shape[1] != 4:
+        raise ValueError(f"points_from_cols: cols must be fp32 [{M} tokens, >= {C * kh * kw}] - the plan's token list x the "
+                         f"channels' {kh * kw} products (got {tuple(cols.shape)} {cols.dtype})")
+    with _timed("points_from_cols", 4.0 * C * P * 5):
+        check(lib().cra5_points_from_cols(_p(cols), _row_stride(cols), M, C, kh * kw, _p(t["contrib"]), t["contrib"].shape[0],
+                                          _p(t["pnode"]), _p(t["rw"]), _p(t["cw"]), P, int(t["method"] == "nearest"),
+                                          _p(mean), _p(std), _p(out), _stream()), "cra5_points_from_cols")
+    return out
+
+
+def points_from_image(x, tables, out=None):
+    """cra5_points_from_image: the contiguous fp32 device image x [C, H, W] at the plan's P points -> fp32 [C, P].  tables:
+    points_tables(Points.taps(H, W) | Points.plan(H, W, ...), device) - the grid (H, W) is the plan's."""
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("points_from_image: x must be a contiguous fp32 [C, H, W] device tensor")
+    C, H, W = x.shape
+    P, out = _points_args("points_from_image", tables, _POINT_TABLES, x, out, C)
+    t = tables
+    if tuple(t["grid"]) != (H, W):
+        raise ValueError(f"points_from_image: the tables were built for a {tuple(t['grid'])} grid, x is {(H, W)}")
+    with _timed("points_from_image", 4.0 * C * P * 5):
+        check(lib().cra5_points_from_image(_p(x), C, H, W, _p(t["rows"]), _p(t["cols"]), _p(t["rw"]), _p(t["cw"]), P,
+                                           int(t["method"] == "nearest"), _p(out), _stream()), "cra5_points_from_image")
+    return out
+
+
 def crop(src, r0, Hb, c0, Wb, out=None):
     """cra5_crop_f32: out[c][i][j] = src[c][r0 + i][(c0 + j) mod Ws] - the box [C, Hb, Wb] of the contiguous image
     src [C, Hs, Ws], columns wrapping at its east edge."""

@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, subset
+from . import points as _points
 from . import regrid as _regrid
 from ._lib import ERR_RANGE, Cra5Error, StreamDesyncError
 from .config import RuntimeConfig, runtime_setting
@@ -256,6 +257,13 @@ class _SlotGate:
 
 class VAEformer(nn.Module):
     SUBSET_CACHE = 8
+    # points=: the sparse route (un-embed of the listed tokens only) runs while its column matrix [M, C' kh kw] is no larger
+    # than the dense route's image [C', H, W]: M * kh * kw <= H * W, M <= 9438 of the 10 368 tokens of the ERA5 grid.
+    # Measured (profiles/points_bench.txt, 268 model, the un-embed step of one frame, sparse / dense in ms): all 268
+    # variables 0.07 / 1.91 at M = 100, 0.56 / 1.77 at 3000, 1.05 / 1.81 at 6000, 1.82 / 1.81 at 9438 (inside each other's
+    # range); six variables 0.06 / 0.10 up to 3000, 0.10 / 0.10 at 9438 - no earlier crossover, the bound stays.  A test
+    # sets 0 to force the dense route.
+    POINT_DENSE_TOKENS = (721 * 1440) // (11 * 10)
 
     def __init__(self, model_version, embed_dim=None, z_channels=None, y_channels=None, sample_posterior=None,
                  pretrained_vae=None, frozen_encoder=None, ddconfig=None, priorconfig=None,
@@ -790,12 +798,13 @@ class VAEformer(nn.Module):
 
     # ---- g_s --------------------------------------------------------------------------------
     def _decode_frame(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None, coarsen=None,
-                      regrid=None):
+                      regrid=None, points=None):
         """y_hat [L, Hp, Wp] -> x_hat [C, H, W] (vaeformer.py:294-300).  channels / box / step (canonical, _subset_args):
         the [len(channels), r1 - r0, nc] slice of that frame - thinned to the global rows % s_lat == 0 / columns % s_lon
         == 0 when step = (s_lat, s_lon) -, bit for bit (_unembed).  coarsen = (k_lat, k_lon) (_coarsen_arg; not with a
         step): the area-weighted mean of that frame at the points step = coarsen would keep (_unembed_windowed).  regrid (a
-        plan, _regrid_arg; on its own): that frame on the plan's target grid (_unembed_windowed).  out: the
+        plan, _regrid_arg; on its own): that frame on the plan's target grid (_unembed_windowed).  points (a plan,
+        _points_arg; with channels only): [len(channels), P], that frame at the plan's points (_unembed_points).  out: the
         contiguous destination of _decoded_shape (one frame of the caller's batch result) - the un-embed writes x_hat
         there; None: a fresh tensor."""
         cfg = self.cfg
@@ -810,7 +819,7 @@ class VAEformer(nn.Module):
             self._block(blk, f"g_s.blocks.{j}", t, t, (self.Hp, self.Wp))
         # the LayerNorm writes plain rows when the whole frame's un-embed takes them (a subset follows the full launch)
         h = self._ln(t, self.g_s.norm, f"h{D}", plain=self._unembed_launch()[3])
-        return self._unembed(h, mean, std, channels, box, step, out, coarsen=coarsen, regrid=regrid)
+        return self._unembed(h, mean, std, channels, box, step, out, coarsen=coarsen, regrid=regrid, points=points)
 
     # ---- un-embed: the whole frame, or chosen channels and / or a lat-lon box of it ---------------------------
     # The transformer runs on the whole grid (global attention); everything after the final LayerNorm is local.  The
@@ -885,6 +894,24 @@ class VAEformer(nn.Module):
         step = self._step_arg(step, box)
         coarsen = self._coarsen_arg(coarsen, box, step)
         return channels, box, step, coarsen, self._regrid_arg(regrid, box, step, coarsen)
+
+    def _points_arg(self, points, box=None, step=None, coarsen=None, regrid=None):
+        """Validate a point list (points.Points | a [P, 2] array of (lat, lon) | its plan | None) against the canonical
+        box / step / coarsen / regrid of _selection_args -> the plan of this model's grid and patches (Points.plan: built
+        once per point list), or None.  ValueError for anything else, and together with any of the four: a point list
+        composes with channels only.  (Beside _selection_args, not in its tuple: that stays the five rectilinear
+        selections.)"""
+        if points is None:
+            return None
+        for name, v in (("box", box), ("step", step), ("coarsen", coarsen), ("regrid", regrid)):
+            if v is not None:
+                raise ValueError(f"points and {name}: pass one of the two - a point list names its own positions")
+        cfg = self.cfg
+        return _points.as_plan(points, *cfg['img_size'], *cfg['patch_size'], *cfg['patch_stride'])
+
+    def _point_tables(self, plan):
+        """ops.points_tables of a canonical plan - built once per point list, cached like the regridding tables."""
+        return self._sub_cached(("pplan", self.device, plan["key"]), self, lambda: ops.points_tables(plan, self.device))
 
     def _regrid_tables(self, plan):
         """ops.regrid_tables of a canonical plan - built once per target grid, cached like the coarsening tables."""
@@ -968,12 +995,15 @@ class VAEformer(nn.Module):
         return self._sub_cached(("stat", t.data_ptr(), t._version, chans), t,
                                 lambda: t.index_select(0, torch.tensor(chans, device=t.device, dtype=torch.long)))
 
-    def _decoded_shape(self, channels=None, box=None, step=None, coarsen=None, regrid=None):
+    def _decoded_shape(self, channels=None, box=None, step=None, coarsen=None, regrid=None, points=None):
         """[C', H', W'] of one decoded frame for the canonical channels / box (_subset_args) and step (_step_arg),
-        coarsen (_coarsen_arg: the shape of step = coarsen) or regrid (_regrid_arg: the target grid's)."""
+        coarsen (_coarsen_arg: the shape of step = coarsen) or regrid (_regrid_arg: the target grid's); [C', P] for
+        points (_points_arg)."""
         step = step if coarsen is None else coarsen
         H, W = self.cfg['img_size']
         C = len(channels) if channels is not None else self.cfg['out_chans']
+        if points is not None:
+            return C, int(points["P"])
         if regrid is not None:
             return C, int(regrid["Ho"]), int(regrid["Wo"])
         r0, r1, _, nc = box if box is not None else (0, H, 0, W)
@@ -1025,13 +1055,16 @@ class VAEformer(nn.Module):
         key, w = "g_s.final", self.g_s.final.weight
         return {"f32": self._wf32, "split": self._wsplit, "plain": self._wplain}[kind](key, w)
 
-    def _unembed(self, h, mean, std, chans, box, step=None, out=None, coarsen=None, regrid=None):
+    def _unembed(self, h, mean, std, chans, box, step=None, out=None, coarsen=None, regrid=None, points=None):
         """The un-embed for channels `chans` (tuple | None: all) inside grid box `box` (tuple | None: the whole grid),
         from the final LayerNorm's output h (SplitMat, or fp32 [N, D] on the exact-f32 engines) -> [C', Hb, Wb], written
         into `out` (_frame_dest: a frame of the caller's batch result - every form below stores straight into it; None:
         a fresh tensor).  chans = box = None is the full decode.  step = (s_lat, s_lon): only the box's points on the
         global lattice rows % s_lat == 0, columns % s_lon == 0 -> [C', Ho, Wo] (_unembed_thinned: the same products, far
-        fewer).  coarsen = (k_lat, k_lon) / regrid (a plan): _unembed_windowed with that plan and its operator."""
+        fewer).  coarsen = (k_lat, k_lon) / regrid (a plan): _unembed_windowed with that plan and its operator.  points (a
+        plan): _unembed_points -> [C', P]."""
+        if points is not None:
+            return self._unembed_points(h, mean, std, chans, points, out)
         if regrid is not None:
             return self._unembed_windowed(h, mean, std, chans, regrid, self._regrid_tables(regrid), ops.regrid, "ue_regrid_src", out)
         if coarsen is not None:
@@ -1172,6 +1205,44 @@ class VAEformer(nn.Module):
         out = self._frame_dest(out, (Cs, plan["Ho"], plan["Wo"]))
         return op(src, tdev, out=out)
 
+    def _unembed_points(self, h, mean, std, chans, plan, out=None):
+        """_unembed at a point list (a canonical plan of _points_arg) -> [C', P].  A grid node is one product of one
+        token, or two on a seam row (points.Points.plan), so the un-embed runs on the plan's token list alone.
+        Sparse route (M = len(tokens) <= POINT_DENSE_TOKENS): gather those token rows verbatim, take the chosen channels'
+        weight rows from the cached copy of the WHOLE weight, run the two-call form's GEMM exactly as _unembed_thinned
+        does - the same MFMA chain over K per product as the full decode's launch - into a per-thread [M, C' kh kw]
+        matrix, and ONE kernel picks the points out of it: upper + lower partner on a seam row, x * std + mean, the
+        full decode's order and arithmetic, then the interpolation.  No image exists on this route.
+        Dense route: the ordinary _unembed of the chosen channels over the whole grid into a per-thread buffer, and the
+        same kernel body reads the nodes from that image.  Both routes give the same bits: each node is the full
+        decode's value, and the interpolation is one fixed float64 expression (csrc/points.hip)."""
+        cfg = self.cfg
+        D = cfg['embed_dim']
+        kh, kw = cfg['patch_size']
+        Himg, Wimg = cfg['img_size']
+        Cs = len(chans) if chans is not None else cfg['out_chans']
+        P = int(plan["P"])
+        tdev = self._point_tables(plan)
+        M = len(plan["tokens"])
+        dest = self._frame_dest(out, (Cs, P))
+        if M > self.POINT_DENSE_TOKENS:
+            img = self._buf("ue_points_img", (Cs, Himg, Wimg))
+            self._unembed(h, mean, std, chans, None, out=img)
+            return ops.points_from_image(img, tdev, out=dest)
+        split = self.gemm_mode == "split"
+        ms, ss = self._stats_of_channels(mean, chans), self._stats_of_channels(std, chans)
+        kind, hi, wide, _ = self._unembed_launch()
+        wfull = self._unembed_weight(kind)
+        wg = wfull if chans is None else self._rows_of_channels(kind, wfull, chans)
+        dst = self._sbuf("ue_a_points", M, D) if split else self._buf("ue_a_points", (M, D))
+        a = ops.gather_token_list(h, dst, tdev["tokens"])
+        cols = self._buf("ue_cols_points", (M, Cs * kh * kw))
+        if split:
+            ops.gemm_nt_split(a, wg, out=cols, hi_only=hi, wide_k=wide)
+        else:
+            ops.gemm_nt(a, wg, out=cols)
+        return ops.points_from_cols(cols, tdev, Cs, mean=ms, std=ss, out=dest)
+
     # ---- latent side: everything between y and the entropy coder ---------------------------
     def _latent_side_frame(self, y, want_lik=False, z_sym_out=None):
         z = self._h_a_frame(y)
@@ -1284,7 +1355,8 @@ class VAEformer(nn.Module):
             return y, self._finite(flag), None
         return self._range_guard(0, run, "encode")
 
-    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None, out=None, coarsen=None, regrid=None):
+    def _g_s_probed(self, y_hat, mean, std, channels=None, box=None, step=None, out=None, coarsen=None, regrid=None,
+                    points=None):
         """g_s of one frame inside the caller's GPU phase -> (x_hat, pinned probe values: test them with _finite once
         the phase has ended).  The residual stream after the last block carries every upstream poison - token-wise, and
         the global attention spreads it (element by element: tests/test_poison_gpu.py.  The one case that is by sign and
@@ -1296,24 +1368,24 @@ class VAEformer(nn.Module):
         channel) is probed as well.  A subset decode (channels / box / step) probes the decoded subset itself:
         every output channel sampled at least min(its element count, 500) times - a coarsened decode likewise: a
         non-finite value of the source stays non-finite through the weighted mean of every window that holds it (a
-        regridded decode likewise).  out:
+        regridded decode likewise; a point decode's [C', P] likewise, all of it when P <= 500).  out:
         _decode_frame's destination - the probe reads the frame where it was written."""
         x_hat = self._decode_frame(y_hat, mean=mean, std=std, channels=channels, box=box, step=step, out=out,
-                                   coarsen=coarsen, regrid=regrid)
+                                   coarsen=coarsen, regrid=regrid, points=points)
         D = self.cfg['embed_dim']
-        whole = channels is None and box is None and step is None and coarsen is None and regrid is None
+        whole = channels is None and box is None and step is None and coarsen is None and regrid is None and points is None
         stride = 2053 if whole else max(1, (x_hat.numel() // x_hat.shape[0]) // 500)
         return x_hat, self._to_host("ok1", self._probe(self._buf(f"t{D}", (self.Hp * self.Wp, D)), (x_hat, stride)))
 
     def _decode_guarded(self, y_hat, mean=None, std=None, channels=None, box=None, step=None, out=None, coarsen=None,
-                        regrid=None):
+                        regrid=None, points=None):
         """g_s of one frame under the range guard: y_hat [L, Hp, Wp] -> x_hat [C, H, W] (or its subset: canonical
-        channels / box of _subset_args, step of _step_arg, coarsen of _coarsen_arg or regrid of _regrid_arg).  out: the
+        channels / box of _subset_args, step of _step_arg, coarsen of _coarsen_arg, regrid of _regrid_arg or points of _points_arg: [C', P]).  out: the
         frame's destination (_decode_frame); a re-run on
         the exact-f32 engines overwrites the same destination."""
         def run():
             with self._gpu_phase():
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen, regrid)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen, regrid, points)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, run, "decode")
 
@@ -1344,7 +1416,8 @@ class VAEformer(nn.Module):
         return y, None, None
 
     @torch.no_grad()
-    def decode_latent(self, y, type='quantized', channels=None, box=None, step=None, coarsen=None, regrid=None):
+    def decode_latent(self, y, type='quantized', channels=None, box=None, step=None, coarsen=None, regrid=None,
+                      points=None):
         """vaeformer.py:294-300.  channels: output channel indices (in the order given); box = (r0, r1, c0, nc): grid rows
         [r0, r1) and nc columns from c0, wrapping at W (subset.grid_box) -> [B, len(channels), r1 - r0, nc], the same
         slice of the full decode bit for bit.  step: a stride, int | (s_lat, s_lon) - of the box (default: the globe) only
@@ -1356,14 +1429,20 @@ class VAEformer(nn.Module):
         section 4): fixed float64 arithmetic, a region's result is the sub-block of the globe's bit for bit.
         regrid: a regrid.Grid or its plan, not together with box / step / coarsen - the full decode on that target grid,
         bilinear or first-order conservative ("Regridding") -> [B, len(channels), Ho, Wo], rows in
-        the grid's own order; fixed float64 arithmetic, a sub-grid's result is the sub-block of the whole grid's."""
+        the grid's own order; fixed float64 arithmetic, a sub-grid's result is the sub-block of the whole grid's.
+        points: a points.Points, a [P, 2] array of (lat, lon) or its plan, with channels only - the full decode at those
+        positions -> [B, len(channels), P], in the order given: "nearest" is the grid node's value bit for bit, "bilinear"
+        regridding's fixed float64 arithmetic on the 1, 2 or 4 nodes round the point ("Point
+        sampling") - the bits of regrid=Grid([lat], [lon]) at that point; only the tokens that hold a node are un-embedded."""
         self._require_gpu()
         channels, box, step, coarsen, regrid = self._selection_args(channels, box, step, coarsen, regrid)
+        points = self._points_arg(points, box, step, coarsen, regrid)
         # the batch result is allocated once and every frame's un-embed stores into its slice (no stack copy)
-        out = torch.empty((y.shape[0],) + self._decoded_shape(channels, box, step, coarsen, regrid), device=self.device,
-                          dtype=torch.float32)
+        out = torch.empty((y.shape[0],) + self._decoded_shape(channels, box, step, coarsen, regrid, points),
+                          device=self.device, dtype=torch.float32)
         for b in range(y.shape[0]):
-            self._decode_guarded(y[b], channels=channels, box=box, step=step, out=out[b], coarsen=coarsen, regrid=regrid)
+            self._decode_guarded(y[b], channels=channels, box=box, step=step, out=out[b], coarsen=coarsen, regrid=regrid,
+                                 points=points)
         return out
 
     @torch.no_grad()
@@ -1503,10 +1582,10 @@ class VAEformer(nn.Module):
             "stream or a different checkpoint looks the same.  Nothing was reconstructed", e.status)
 
     def _decompress_frame(self, y_string, z_string, shape, reconstruct, mean=None, std=None, channels=None, box=None,
-                          step=None, out=None, coarsen=None, regrid=None):
+                          step=None, out=None, coarsen=None, regrid=None, points=None):
         """host: decode z | GPU: h_s, indexes | host: decode y | GPU: de-quantise (+ g_s: the whole frame, or the
-        canonical channels / box of _subset_args, step of _step_arg, coarsen of _coarsen_arg or regrid of _regrid_arg; out: the
-        reconstruction's destination, _decode_frame)."""
+        canonical channels / box of _subset_args, step of _step_arg, coarsen of _coarsen_arg, regrid of _regrid_arg or points of
+        _points_arg; out: the reconstruction's destination, _decode_frame)."""
         eb, gc = self.entropy_bottleneck, self.gaussian_conditional
         Cz = eb.channels
         zh, zw = int(shape[0]), int(shape[1])
@@ -1581,34 +1660,35 @@ class VAEformer(nn.Module):
                     y_hat = ops.gaussian_conditional(scales, means, gc.scale_table, sym_in=y_sym, want=("y_hat",))["y_hat"]
                 if not reconstruct:
                     return y_hat, True, None
-                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen, regrid)
+                x_hat, flag = self._g_s_probed(y_hat, mean, std, channels, box, step, out, coarsen, regrid, points)
             return x_hat, self._finite(flag), None
         return self._range_guard(1, gpu_side, "decompress")
 
     @torch.no_grad()
     def decompress(self, strings, shape, return_format='reconstructed', channels=None, box=None, step=None, coarsen=None,
-                   regrid=None):
-        """vaeformer.py:378-400.  channels / box / step / coarsen / regrid: a subset of the reconstruction, or the
-        reconstruction on another grid (decode_latent)."""
+                   regrid=None, points=None):
+        """vaeformer.py:378-400.  channels / box / step / coarsen / regrid / points: a subset of the reconstruction, the
+        reconstruction on another grid or at a list of points (decode_latent)."""
         self._require_gpu()
         assert isinstance(strings, list) and len(strings) == 2
         rec = return_format != 'latent'
         if not rec and (channels is not None or box is not None or step is not None or coarsen is not None
-                        or regrid is not None):
+                        or regrid is not None or points is not None):
             raise ValueError("decompress: return_format='latent' returns the latent; channels / box / step / coarsen / "
-                             "regrid select a subset of the reconstruction")
+                             "regrid / points select a subset of the reconstruction")
         channels, box, step, coarsen, regrid = self._selection_args(channels, box, step, coarsen, regrid)
+        points = self._points_arg(points, box, step, coarsen, regrid)
         self.entropy_bottleneck._check()
         self.gaussian_conditional._check()
         B = len(strings[0])
         if not rec:
             return torch.stack([self._decompress_frame(strings[0][b], strings[1][b], shape, False) for b in range(B)])
         # the batch result is allocated once and every frame's un-embed stores into its slice (no stack copy)
-        out = torch.empty((B,) + self._decoded_shape(channels, box, step, coarsen, regrid), device=self.device,
+        out = torch.empty((B,) + self._decoded_shape(channels, box, step, coarsen, regrid, points), device=self.device,
                           dtype=torch.float32)
         for b in range(B):
             self._decompress_frame(strings[0][b], strings[1][b], shape, True, channels=channels, box=box, step=step,
-                                   out=out[b], coarsen=coarsen, regrid=regrid)
+                                   out=out[b], coarsen=coarsen, regrid=regrid, points=points)
         return {"x_hat": out}
 
     @torch.no_grad()

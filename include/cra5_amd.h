@@ -330,6 +330,33 @@ int cra5_strided_scatter_f32(const float *g, size_t g_elems, const int *rows, co
                              int n_rc, int n_cc, const float *mean, const float *stdv, float *x, int C, int Ho, int Wo,
                              void *stream);
 
+/* Point decode (csrc/points.hip; cra5_amd/points.py Points.plan): the decoded frame at P (lat, lon) positions, [C][P].
+ * cra5_gather_token_list: dst row r <- src row tok[r] (tok: int32 device [n_tok]), verbatim in 16-byte units - split,
+ * plain and fp32 rows alike; cra5_gather_token_rows' alignment rules.  A tok[r] outside [0, n_src_rows) reads nothing and
+ * fills the row with 0xFF bytes (a NaN as f16 and as fp32).
+ * cra5_points_from_cols: the points out of the two-call un-embed's column matrix cols [M][pitch] (pitch in floats,
+ * >= C * taps_per_channel; channel c's kh * kw products at column c * taps_per_channel) of the M gathered tokens.  Device
+ * tables: nodes int32 [n_nodes][4] = (m0, tap0, m1, tap1), the node's value
+ *   v = cols[m0][c * tpc + tap0];  if (m1 >= 0) v = v + cols[m1][c * tpc + tap1];  if (mean) v = v * std[c] + mean[c]
+ * (a seam row's UPPER partner first: cra5_strided_scatter_f32's expression, order and contraction); pnode int32 [P][4]:
+ * the node of (row tap t, column tap u) at entry 2 t + u, -1 = no such tap; rw, cw fp64 [P][2]: the taps' weights.
+ * nearest != 0: out[c][p] = v(pnode[p][0]), copied (-0.0 and NaN payloads survive; rw / cw may be NULL).  Otherwise, in
+ * fp64, every operation rounded on its own (no contraction), sums from 0.0, north to south over west to east:
+ *   out[c][p] = (float) sum_t rw[p][t] * (sum_u cw[p][u] * (double)v(node[p][t][u]))     - cra5_regrid_f32's arithmetic.
+ * cra5_points_from_image: the same two rules with the node value read from the image x [C][H][W]; rows, cols int32 [P][2]:
+ * the row taps / column taps, -1 = no second tap.
+ * A table entry outside its source (a node outside [0, n_nodes), a token row outside [0, M), a tap outside [0, tpc), a
+ * row / column outside the image) is never read: the point becomes NaN.  CRA5_ERR_ARG, before any device work, for NULL /
+ * misaligned pointers, sizes <= 0, C > 65535, C * P or C * taps_per_channel or H * W beyond int32, C * taps_per_channel >
+ * pitch, mean without std. */
+int cra5_gather_token_list(const void *src, size_t src_pitch_bytes, void *dst, size_t dst_pitch_bytes, size_t row_bytes,
+                           int n_src_rows, const int *tok, int n_tok, void *stream);
+int cra5_points_from_cols(const float *cols, size_t pitch, int M, int C, int taps_per_channel, const int *nodes,
+                          int n_nodes, const int *pnode, const double *rw, const double *cw, int P, int nearest,
+                          const float *mean, const float *stdv, float *out, void *stream);
+int cra5_points_from_image(const float *x, int C, int H, int W, const int *rows, const int *cols, const double *rw,
+                           const double *cw, int P, int nearest, float *out, void *stream);
+
 /* Area-weighted coarsening (csrc/window_reduce.hip; cra5_amd/subset.py coarsen_plan): the first-order
  * conservative regrid of src - fp32 [C_src][Hs][Ws], contiguous, whose element [.][0][0] is the GLOBAL grid point (src_r0,
  * src_c0) of an H x W grid; whole_circle != 0: Ws == W and src_c0 == 0, windows wrap at the east edge - onto the Ho x Wo
